@@ -9,6 +9,14 @@ source and target in the device symmetric heap (inputs resident in HBM when
 the timed region starts). K steps are bracketed by shmem_barrier_all + a
 device synchronize on both sides; the time is the max over PEs.
 
+A plain run does only that: it sets up, warms up, times the K steps and
+prints the result line (metric, value, unit, higher_is_better, dtype,
+ms_per_step and the run's configuration). `--dump-outputs DIR` also writes
+what the last timed step left in each PE's target as DIR/target_pe<k>.npy
+(dump_outputs). Everything below (the roofline, the CPU baseline, the checks
+against the oracle, the other sizes, operators, heaps and schedules) is
+measured only with `--full`, whose line carries the plain run's keys too.
+
 value = N * 256 MiB / t_step / 2^30 (whole job); per-PE S/t_step is also
 printed. roofline: the dominant kernel of the schedule the library actually
 ran (shmemx_last_call_info: its name as rocprofv3 prints it, its sources,
@@ -70,6 +78,103 @@ def synth_bits(pe, idx):
         z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
         out = out | (z ^ (z >> np.uint64(31)))
     return out.view(np.int64)
+
+
+DUMP_BUDGET = 48 << 20   # bytes of .npy over all PEs (--dump-outputs)
+
+
+def dump_outputs(shm, outdir, dst, n, me, npes, host=False):
+    """--dump-outputs: what the caller of the timed call holds after the last
+    timed step -- this PE's target array of n doubles -- as
+    outdir/target_pe<me>.npy (float64). All PEs together write at most
+    DUMP_BUDGET bytes: a target larger than its share is written as a fixed
+    sample, the elements at the sorted indices drawn by
+    numpy.random.default_rng(20240607) (the same on every PE and in every
+    run; the inputs are synth's, so two builds' files compare element for
+    element)."""
+    os.makedirs(outdir, exist_ok=True)
+    if host:
+        import ctypes
+        got = np.empty(n, dtype=np.float64)
+        ctypes.memmove(got.ctypes.data, dst, n * 8)
+    else:
+        got = shm.get(dst, n, "double")
+    m = DUMP_BUDGET // 8 // npes
+    if n > m:
+        got = got[np.sort(np.random.default_rng(20240607).integers(0, n, m))]
+    np.save(os.path.join(outdir, "target_pe%d.npy" % me), np.ascontiguousarray(got, dtype=np.float64))
+
+
+def plain_run(args):
+    """The run without --full: set up as the full run does (the same heap
+    sizes, allocations and inputs, so the buffers lie where the full run's
+    do), warm up, time the K steps between barrier + device synchronize,
+    write the outputs if asked, print the result line."""
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    if world != args.gpus:
+        raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}")
+    S = args.mib << 20
+    n = S // 8
+    pairs = ROT_PAIRS if world == 1 and not args.host and not args.no_rotating else 1
+    heap = 2 * S * pairs
+    if not args.host:
+        heap = max(heap, 3 * S)
+    os.environ.setdefault("SHMEM_DEVICE_HEAP_SIZE", str(heap + (64 << 20)))
+    os.environ.setdefault("SHMEM_DEVICE_SCRATCH_SIZE", str(96 << 20))
+    os.environ.setdefault("SHMEM_BARRIER_TIMEOUT", "120")
+    os.environ.setdefault("SHMEM_BOOTSTRAP_TIMEOUT", "600")
+    shm = shmem_reduce.Shmem()
+    shm.init()
+    rccl_fallback = shm.n_pes() > 1 and shm.lib.shmemx_get_reduce_algorithm() == shmem_reduce.ALGORITHMS["rccl"] \
+        and args.algorithm != "rccl"
+    shm.set_algorithm(args.algorithm)
+    me, npes = shm.my_pe(), shm.n_pes()
+    x = synth(me, np.arange(n, dtype=np.uint64))
+    if args.host:
+        import ctypes
+        src, dst = shm.malloc(S), shm.malloc(S)
+        ctypes.memmove(src, x.ctypes.data, S)
+    else:
+        src, dst = shm.malloc_device(S), shm.malloc_device(S)
+        shm.put(src, x)
+    del x
+    loop = shmem_reduce.bench_loop()
+    loop(dst, src, n, 0, 0, npes, None, shm._psync_ptr, args.warmup)
+    shm.barrier_all()
+    shm.sync()
+    t0 = time.perf_counter()
+    loop(dst, src, n, 0, 0, npes, None, shm._psync_ptr, args.steps)
+    shm.sync()
+    t_local = time.perf_counter() - t0
+    shm.barrier_all()
+    if args.dump_outputs:
+        dump_outputs(shm, args.dump_outputs, dst, n, me, npes, host=args.host)
+    tbuf, tout = np.array([t_local], dtype=np.float64), np.zeros(1, dtype=np.float64)
+    shm.to_all("max", "double", tout.ctypes.data, tbuf.ctypes.data, 1, 0, 0, npes)
+    t_step = float(tout[0]) / args.steps
+    if me == 0:
+        print(json.dumps({
+            "metric": ("GiB/s reduced (host-staged incl. H2D/D2H), shmem_double_sum_to_all @256MiB" if args.host else
+                       "GiB/s reduced (device-resident), shmem_double_sum_to_all @256MiB, 1/2/4/8 GPU"),
+            "value": round(npes * S / t_step / GIB, 2), "unit": "GiB/s", "n_gpus": npes, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": round(t_step * 1e3, 4), "higher_is_better": True,
+            "scaling": "weak", "vs_baseline": None, "dtype": "f64",
+            "data": "synthetic (splitmix64 full-mantissa doubles, device-resident symmetric heap)",
+            "config": {"workload": f"shmem_double_sum_to_all, {npes} PE = {npes} GPU, {args.mib} MiB "
+                                   f"{'host-memory (staged)' if args.host else 'device-resident'} array per PE",
+                       "nreduce": n, "bytes_per_pe": S,
+                       "algorithm": "rccl (fallback: P2P self-test failed)" if rccl_fallback else args.algorithm,
+                       "parallelism": f"pe{npes}"},
+            "per_pe_gib_s": round(S / t_step / GIB, 2), "full": False,
+            "outputs": args.dump_outputs and "target_pe<k>.npy, one per PE (dump_outputs)",
+            "total_s": round(time.perf_counter() - T_START, 2)}), flush=True)
+    if args.host:
+        shm.free(dst)
+        shm.free(src)
+    else:
+        shm.free_device(dst)
+        shm.free_device(src)
+    shm.finalize()
 
 
 def cpu_model():
@@ -1057,6 +1162,14 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--mib", type=int, default=256, help="MiB per PE")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline, measure and check everything else the line can carry: the CPU "
+                         "baseline, the roofline, the per-call distribution, the checks against the oracle and every "
+                         "other leg (the --no-* options below choose among them); without it only the K steps are "
+                         "timed")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps write each PE's target as DIR/target_pe<k>.npy (float64; a fixed "
+                         "sample when the targets exceed %d MiB together)" % (DUMP_BUDGET >> 20))
     ap.add_argument("--algorithm", default=os.environ.get("SHMEM_REDUCE_ALGORITHM", "auto"))
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -1099,6 +1212,8 @@ def main():
                     help="N = 1: skip the host_staged leg (the same call on page-locked host arrays, with the "
                          "same run's PCIe ceiling)")
     args = ap.parse_args()
+    if not args.full:
+        return plain_run(args)
 
     # wall time of every leg (legs_s in the line), and optional legs that fail
     # become an {"error": ...} entry instead of ending the headline line. A leg
@@ -1245,6 +1360,8 @@ def main():
     shm.sync()
     t_local = time.perf_counter() - t0
     shm.barrier_all()
+    if args.dump_outputs:   # before any later leg writes the target
+        dump_outputs(shm, args.dump_outputs, dst, n, me, npes, host=args.host)
 
     # kernel duration: the same K steps again with a HIP event pair attached to
     # each dominant kernel launch (hipExtLaunchKernel stamps on the library's
@@ -1839,6 +1956,7 @@ def main():
                        "algorithm": "rccl (fallback: P2P self-test failed)" if rccl_fallback else args.algorithm,
                        "parallelism": f"pe{npes}"},
             "per_pe_gib_s": round(S / t_step / GIB, 2),
+            "full": True,
             "per_call": call_dist,
             "fixed_cost": None if t_tiny is None else {
                 "tiny_call_us": round(t_tiny * 1e6, 2),

@@ -1,6 +1,8 @@
 """GPU: bench.py's contract with the driver, on a short run -- exactly one
-JSON line on stdout (rank 0), the metric/config of BASELINE.json, a bit-exact
-check, and the roofline / cpu_baseline / op_coverage records. The N = 2 run
+JSON line on stdout (rank 0), the metric/config of BASELINE.json; a plain run
+carries the headline alone (and writes its target with --dump-outputs), a
+--full run also a bit-exact check and the roofline / cpu_baseline /
+op_coverage records. The N = 2 run
 shares the one test GPU and forces the RCCL comparison, which then fails
 (RCCL refuses two ranks on one device): the line must still come out, with
 the comparison marked as skipped and the target re-checked on the default
@@ -94,8 +96,29 @@ def common(d, n):
     assert g["schedule"] == ("stream-identity" if n == 1 else "stream-fused-oneshot"), g
 
 
+def test_bench_plain_run_times_only_its_steps_and_dumps_the_target(tmp_path):
+    """Without --full the bench sets up, warms up, times its K steps and prints
+    the headline keys, none of the other legs' records; --dump-outputs writes
+    the target of the last timed step (here a fixed sample of its 32 Mi
+    doubles, within 64 MB), which at N = 1 is the source, bit for bit."""
+    import numpy as np
+    import bench
+    out = tmp_path / "dump"
+    d = run([sys.executable, "bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2", "--dump-outputs", str(out)])
+    assert d["metric"] == METRIC and d["unit"] == "GiB/s" and d["higher_is_better"] is True and d["dtype"] == "f64"
+    assert d["n_gpus"] == 1 and d["steps"] == 7 and d["warmup"] == 2 and d["full"] is False, d
+    assert d["ms_per_step"] > 0 and abs(d["value"] - 0.25 / (d["ms_per_step"] * 1e-3)) < 0.005 * d["value"], d
+    assert not {"cpu_baseline", "roofline", "check", "kernels", "op_coverage", "small_call", "legs_s"} & set(d), d
+    assert os.listdir(out) == ["target_pe0.npy"]
+    got = np.load(out / "target_pe0.npy")
+    n = d["config"]["nreduce"]
+    assert got.dtype == np.float64 and got.ndim == 1 and got.nbytes <= 64 << 20 and 1 << 20 < len(got) < n, got.shape
+    idx = np.sort(np.random.default_rng(20240607).integers(0, n, len(got)))
+    assert (got.view(np.uint64) == bench.synth(0, idx.astype(np.uint64)).view(np.uint64)).all()
+
+
 def test_bench_one_gpu_line():
-    d = run([sys.executable, "bench.py", "--steps", "5", "--warmup", "2", "--cpu-seconds", "1", "--kernel-reps", "5"])
+    d = run([sys.executable, "bench.py", "--full", "--steps", "5", "--warmup", "2", "--cpu-seconds", "1", "--kernel-reps", "5"])
     common(d, 1)
     cb = d["cpu_baseline"]
     # the headline's shape: 1 PE on 1 core; the other PE counts as sub-records
@@ -161,7 +184,7 @@ def test_bench_two_ranks_line_with_failed_rccl_comparison(tmp_path):
     log = tmp_path / "trace.log"
     env = dict(os.environ, SHMEM_LOG_LEVELS="REDUCTION", SHMEM_LOG_FILE=str(log))
     d = run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
-             "--master-addr", "127.0.0.1", "--master-port", str(free_port()), "bench.py", "--gpus", "2", "--steps",
+             "--master-addr", "127.0.0.1", "--master-port", str(free_port()), "bench.py", "--full", "--gpus", "2", "--steps",
              "5", "--warmup", "2", "--force-rccl-compare", "--cpu-seconds", "2"], env=env)
     common(d, 2)
     assert "error" in d["rccl_compare"], d["rccl_compare"]
@@ -245,6 +268,29 @@ def test_bench_two_ranks_line_with_failed_rccl_comparison(tmp_path):
 
 
 @pytest.mark.multipe
+def test_bench_plain_run_two_ranks_dumps_every_pe_target(tmp_path):
+    """The plain run at N = 2 (16 MiB per PE, the ranks sharing the test GPU):
+    one line from rank 0, the step time the max over PEs, and each PE's whole
+    target written, equal bit for bit to the reference's result for that PE."""
+    import numpy as np
+    import bench
+    import oracle
+    out = tmp_path / "dump"
+    d = run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
+             "--master-addr", "127.0.0.1", "--master-port", str(free_port()), "bench.py", "--gpus", "2", "--steps",
+             "3", "--warmup", "1", "--mib", "16", "--dump-outputs", str(out)])
+    assert d["n_gpus"] == 2 and d["steps"] == 3 and d["full"] is False and d["ms_per_step"] > 0 and d["value"] > 0, d
+    assert sorted(os.listdir(out)) == ["target_pe0.npy", "target_pe1.npy"]
+    n = d["config"]["nreduce"]
+    idx = np.arange(n, dtype=np.uint64)
+    srcs = [bench.synth(p, idx) for p in range(2)]
+    for me in range(2):
+        got = np.load(out / f"target_pe{me}.npy")
+        assert got.dtype == np.float64 and got.shape == (n,), got.shape
+        assert (got.view(np.uint64) == oracle.reduce_pe("sum", "double", srcs, me).view(np.uint64)).all(), me
+
+
+@pytest.mark.multipe
 def test_bench_line_survives_a_dying_extra_legs_job():
     """The N > 1 legs that had never run with one GPU per PE run in a child
     job (tools/extra_legs.py) so that a fatal error there cannot cost the
@@ -253,7 +299,7 @@ def test_bench_line_survives_a_dying_extra_legs_job():
     entry under exactly those three legs and the headline intact."""
     env = dict(os.environ, SHMEM_TEST_EXTRA_LEGS_ABORT="1")
     d = run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
-             "--master-addr", "127.0.0.1", "--master-port", str(free_port()), "bench.py", "--gpus", "2", "--steps",
+             "--master-addr", "127.0.0.1", "--master-port", str(free_port()), "bench.py", "--full", "--gpus", "2", "--steps",
              "5", "--warmup", "2", "--no-cpu-baseline", "--no-small", "--no-ops", "--no-threshold-sweep",
              "--no-rccl-compare"], env=env)
     assert d["value"] > 0 and d["check"].startswith("bit-exact"), d
@@ -275,7 +321,7 @@ def test_bench_xgmi_legs_rehearsal_four_ranks():
     every variant's outputs equal the library's, and the figures stay out of
     the roofline (a rehearsal, marked so)."""
     d = run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4",
-             "--master-addr", "127.0.0.1", "--master-port", str(free_port()), "bench.py", "--gpus", "4", "--steps",
+             "--master-addr", "127.0.0.1", "--master-port", str(free_port()), "bench.py", "--full", "--gpus", "4", "--steps",
              "5", "--warmup", "2", "--mib", "64", "--force-xgmi-legs", "--no-cpu-baseline", "--no-small", "--no-ops",
              "--no-threshold-sweep", "--no-rccl-compare", "--no-external", "--no-link-probe", "--no-collectives"],
             timeout=400)
