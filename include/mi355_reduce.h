@@ -92,6 +92,17 @@ int mi355_combine_orders (int op, int dtype, void *const *dsts, const void *cons
 int mi355_copy_segments (void *const *dsts, const void *const *srcs,
                          const size_t *nbytes, int nseg, void *stream);
 
+/* nseg independent strided blocks in ONE launch (shmem_alltoalls):
+ *   dsts[i][k * dst_stride] = srcs[i][k * src_stride]    for k < nelems
+ * with elements of elem_size 4 or 8 bytes and strides in elements, >= 1.
+ * nseg <= 64; pointers element-aligned; sources may be peer pointers, the
+ * targets are local. A side of stride 1 moves as 16-byte vectors (peeled to
+ * its 128-byte line); on a side of stride > 1 consecutive lanes take
+ * consecutive elements. Both strides 1 is mi355_copy_segments. Every element
+ * of a target between and after the strided ones is left alone. */
+int mi355_strided_pull (int elem_size, void *const *dsts, const void *const *srcs,
+                        ptrdiff_t dst_stride, ptrdiff_t src_stride, size_t nelems, int nseg, void *stream);
+
 /* The two-member all-gather of a float/double sum or product: dst[i] =
  * own[i] quieted where own[i] is a NaN, else peer[i] (the other member's shard,
  * folded in its order: the same bits as this member's order except where

@@ -63,6 +63,14 @@ void pshmem_collect64 (void *target, const void *source, size_t nelems, int PE_s
                        int PE_size, long *pSync);
 void pshmem_collect32 (void *target, const void *source, size_t nelems, int PE_start, int logPE_stride,
                        int PE_size, long *pSync);
+void pshmem_alltoall32 (void *target, const void *source, size_t nelems, int PE_start, int logPE_stride,
+                        int PE_size, long *pSync);
+void pshmem_alltoall64 (void *target, const void *source, size_t nelems, int PE_start, int logPE_stride,
+                        int PE_size, long *pSync);
+void pshmem_alltoalls32 (void *target, const void *source, ptrdiff_t dst, ptrdiff_t sst, size_t nelems,
+                         int PE_start, int logPE_stride, int PE_size, long *pSync);
+void pshmem_alltoalls64 (void *target, const void *source, ptrdiff_t dst, ptrdiff_t sst, size_t nelems,
+                         int PE_start, int logPE_stride, int PE_size, long *pSync);
 
     void pshmem_short_sum_to_all (short *target, short *source,
             int nreduce, int PE_start, int logPE_stride, int PE_size,

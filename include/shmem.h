@@ -117,6 +117,22 @@ void shmem_collect64 (void *target, const void *source, size_t nelems, int PE_st
 void shmem_collect32 (void *target, const void *source, size_t nelems, int PE_start, int logPE_stride,
                       int PE_size, long *pSync);
 
+/* ---- all-to-all (reference src/shmem.h:1785-1805); sources in the device
+ *      symmetric heap or the symmetric host heap. Member i's block m lands
+ *      as block i of member m's target, m and i being indices IN THE ACTIVE
+ *      SET; the strided form places and reads elements dst / sst (>= 1)
+ *      elements apart and leaves every other element of the target alone. ---- */
+#define SHMEM_ALLTOALL_SYNC_SIZE (128L / SHMEM_INTERNAL_F2C_SCALE)
+#define SHMEM_ALLTOALLS_SYNC_SIZE (128L / SHMEM_INTERNAL_F2C_SCALE)
+void shmem_alltoall32 (void *target, const void *source, size_t nelems, int PE_start, int logPE_stride,
+                       int PE_size, long *pSync);
+void shmem_alltoall64 (void *target, const void *source, size_t nelems, int PE_start, int logPE_stride,
+                       int PE_size, long *pSync);
+void shmem_alltoalls32 (void *target, const void *source, ptrdiff_t dst, ptrdiff_t sst, size_t nelems,
+                        int PE_start, int logPE_stride, int PE_size, long *pSync);
+void shmem_alltoalls64 (void *target, const void *source, ptrdiff_t dst, ptrdiff_t sst, size_t nelems,
+                        int PE_start, int logPE_stride, int PE_size, long *pSync);
+
 /* ---- reductions: target = op-fold over the active set of source ---- */
     void shmem_short_sum_to_all (short *target, short *source,
             int nreduce, int PE_start, int logPE_stride, int PE_size,

@@ -12,6 +12,8 @@
 #ifndef SHMEM_FORTRAN_H
 #define SHMEM_FORTRAN_H 1
 
+#include <stddef.h>
+
 #ifdef __cplusplus
 # include <complex>
 # define SHMEM_F_COMPLEX(T) std::complex<T>
@@ -107,6 +109,15 @@ void shmem_comp4_prod_to_all_ (SHMEM_F_COMPLEX (float) *target, SHMEM_F_COMPLEX 
         int *PE_start, int *logPE_stride, int *PE_size, SHMEM_F_COMPLEX (float) *pWrk, int *pSync);
 void shmem_comp8_prod_to_all_ (SHMEM_F_COMPLEX (double) *target, SHMEM_F_COMPLEX (double) *source, int *nreduce,
         int *PE_start, int *logPE_stride, int *PE_size, SHMEM_F_COMPLEX (double) *pWrk, int *pSync);
+/* all-to-all (reference src/fortran/fortran.c:1272-1321) */
+void shmem_alltoall32_ (void *target, const void *source, int *nelems,
+        int *PE_start, int *logPE_stride, int *PE_size, int *pSync);
+void shmem_alltoall64_ (void *target, const void *source, int *nelems,
+        int *PE_start, int *logPE_stride, int *PE_size, int *pSync);
+void shmem_alltoalls32_ (void *target, const void *source, ptrdiff_t *dst, ptrdiff_t *sst, int *nelems,
+        int *PE_start, int *logPE_stride, int *PE_size, int *pSync);
+void shmem_alltoalls64_ (void *target, const void *source, ptrdiff_t *dst, ptrdiff_t *sst, int *nelems,
+        int *PE_start, int *logPE_stride, int *PE_size, int *pSync);
 
 /* strong (PSHMEM) names */
 void pstart_pes_ (int *npes);
@@ -195,6 +206,14 @@ void pshmem_comp4_prod_to_all_ (SHMEM_F_COMPLEX (float) *target, SHMEM_F_COMPLEX
 void pshmem_comp8_prod_to_all_ (SHMEM_F_COMPLEX (double) *target, SHMEM_F_COMPLEX (double) *source, int *nreduce,
         int *PE_start, int *logPE_stride, int *PE_size, SHMEM_F_COMPLEX (double) *pWrk, int *pSync);
 
+void pshmem_alltoall32_ (void *target, const void *source, int *nelems,
+        int *PE_start, int *logPE_stride, int *PE_size, int *pSync);
+void pshmem_alltoall64_ (void *target, const void *source, int *nelems,
+        int *PE_start, int *logPE_stride, int *PE_size, int *pSync);
+void pshmem_alltoalls32_ (void *target, const void *source, ptrdiff_t *dst, ptrdiff_t *sst, int *nelems,
+        int *PE_start, int *logPE_stride, int *PE_size, int *pSync);
+void pshmem_alltoalls64_ (void *target, const void *source, ptrdiff_t *dst, ptrdiff_t *sst, int *nelems,
+        int *PE_start, int *logPE_stride, int *PE_size, int *pSync);
 #ifdef __cplusplus
 }
 #endif

@@ -18,6 +18,11 @@
  *       nelems elements land at offset i*nelems of every member's target
  *   shmem_collect32/64     src/collect/collect-linear.c:60-156: like fcollect
  *       with per-PE counts; offsets are the running sum in active-set order
+ *   shmem_alltoall32/64, shmem_alltoalls32/64   src/alltoall/alltoall-linear.c:
+ *       member i's block m lands as block i of member m's target, the strided
+ *       form dst / sst elements apart (see alltoall_bytes for the one
+ *       deliberate deviation: blocks are numbered by the index in the active
+ *       set, not by the global PE number)
  *
  * The remote side of put/get, and every collective's source, is symmetric:
  * in the device symmetric heap (shmemx_malloc_device), which peers read over
@@ -576,6 +581,250 @@ void pshmem_collect64 (void *target, const void *source, size_t nelems, int PE_s
     collect_bytes ("shmem_collect64", target, source, 8 * nelems, PE_start, logPE_stride, PE_size);
 }
 
+/* ---------------------------------------------------------------------- */
+/* all-to-all                                                              */
+/* ---------------------------------------------------------------------- */
+/* d[k * dst] = s[k * sst], k < n, in host memory (elements of es = 4 or 8 bytes) */
+static void host_strided_copy (void *d, const void *s, size_t es, ptrdiff_t dst, ptrdiff_t sst, size_t n)
+{
+    if (dst == 1 && sst == 1) {
+        memmove (d, s, n * es);
+    } else if (es == 4) {
+        for (size_t k = 0; k < n; ++k)
+            ((uint32_t *) d)[(ptrdiff_t) k * dst] = ((const uint32_t *) s)[(ptrdiff_t) k * sst];
+    } else {
+        for (size_t k = 0; k < n; ++k)
+            ((uint64_t *) d)[(ptrdiff_t) k * dst] = ((const uint64_t *) s)[(ptrdiff_t) k * sst];
+    }
+}
+
+/* k blocks of nelems elements into device memory: the copy kernel when both
+ * strides are 1 (mi355_strided_pull hands those on), the strided kernel
+ * otherwise, 64 blocks per launch. wait as in pull_impl. */
+static void a2a_launch (const char *fn, int es, void **dsts, const void **srcs, ptrdiff_t dst, ptrdiff_t sst,
+                        size_t nelems, int k, int wait)
+{
+    shmemi_peer_acquire (shmemi.stream); /* the sources are other PEs' memory */
+    for (int base = 0; base < k; base += 64) {
+        const int g = k - base < 64 ? k - base : 64;
+        if (base + g == k && wait)
+            shmemi_arm_signal ();
+        shmemi_timed_begin ();
+        const int rc = mi355_strided_pull (es, dsts + base, srcs + base, dst, sst, nelems, g, shmemi.stream);
+        shmemi_timed_end ();
+        if (rc != 0)
+            shmemi_fatal ("%s: %s kernel launch failed: %d", fn, dst == 1 && sst == 1 ? "copy" : "strided", rc);
+    }
+    if (wait)
+        shmemi_wait_signal ();
+}
+
+/* Strided blocks from device sources into HOST memory (the host heap or
+ * pageable memory): the strided kernel packs as many blocks as fit into
+ * scratch C, one copy brings them to the host, and host loops place the
+ * elements dst apart -- the gap elements of the target are never written.
+ * Returns with everything in place. */
+static void a2a_staged (const char *fn, int es, void **dsts, const void **srcs, ptrdiff_t dst, ptrdiff_t sst,
+                        size_t nelems, int k)
+{
+    char *scratch = shmemi.heap + shmemi.scratch_off + 2 * shmemi.scratch_chunk; /* scratch C */
+    const size_t cap = shmemi.scratch_chunk / (size_t) es;                        /* elements per pass */
+    if (cap == 0)
+        shmemi_fatal ("%s: no device scratch to stage a host target through", fn);
+    const size_t piece = nelems < cap ? nelems : cap; /* elements of one block per pass */
+    size_t per = cap / piece;                         /* blocks per pass */
+    if (per > 64)
+        per = 64;
+    char *tmp = (char *) malloc (per * piece * (size_t) es);
+    if (tmp == NULL)
+        shmemi_fatal ("out of host memory");
+    shmemi_peer_acquire (shmemi.stream);
+    for (size_t k0 = 0; k0 < nelems; k0 += piece) {
+        const size_t cnt = nelems - k0 < piece ? nelems - k0 : piece;
+        for (int base = 0; base < k; base += (int) per) {
+            const int g = k - base < (int) per ? k - base : (int) per;
+            void *pd[64];
+            const void *ps[64];
+            for (int j = 0; j < g; ++j) {
+                pd[j] = scratch + (size_t) j * cnt * (size_t) es;
+                ps[j] = (const char *) srcs[base + j] + (ptrdiff_t) k0 * sst * es;
+            }
+            const int rc = mi355_strided_pull (es, pd, ps, 1, sst, cnt, g, shmemi.stream);
+            if (rc != 0)
+                shmemi_fatal ("%s: strided kernel launch failed: %d", fn, rc);
+            SHMEMI_HIP (hipMemcpyAsync (tmp, scratch, (size_t) g * cnt * (size_t) es, hipMemcpyDeviceToHost,
+                                        shmemi.stream));
+            SHMEMI_HIP (hipStreamSynchronize (shmemi.stream));
+            for (int j = 0; j < g; ++j)
+                host_strided_copy ((char *) dsts[base + j] + (ptrdiff_t) k0 * dst * es, tmp + (size_t) j * cnt * es,
+                                   (size_t) es, dst, 1, cnt);
+        }
+    }
+    free (tmp);
+}
+
+/* Blocks out of peers' symmetric HOST heap segments (the pull_host pattern):
+ * host loops into host memory; into device memory a copy per block when both
+ * sides are contiguous, else the elements packed on the host, copied to
+ * scratch C and spread by the strided kernel. */
+static void a2a_from_host (const char *fn, int es, void **dsts, const void **srcs, ptrdiff_t dst, ptrdiff_t sst,
+                           size_t nelems, int k)
+{
+    if (host_side (dsts[0])) {
+        for (int i = 0; i < k; ++i)
+            host_strided_copy (dsts[i], srcs[i], (size_t) es, dst, sst, nelems);
+        return;
+    }
+    need_gpu (fn);
+    if (dst == 1 && sst == 1) {
+        for (int i = 0; i < k; ++i)
+            SHMEMI_HIP (hipMemcpyAsync (dsts[i], srcs[i], nelems * (size_t) es, hipMemcpyDefault, shmemi.stream));
+        SHMEMI_HIP (hipStreamSynchronize (shmemi.stream));
+        return;
+    }
+    char *scratch = shmemi.heap + shmemi.scratch_off + 2 * shmemi.scratch_chunk; /* scratch C */
+    const size_t cap = shmemi.scratch_chunk / (size_t) es;
+    if (cap == 0)
+        shmemi_fatal ("%s: no device scratch to stage a host source through", fn);
+    const size_t piece = nelems < cap ? nelems : cap;
+    char *tmp = (char *) malloc (piece * (size_t) es);
+    if (tmp == NULL)
+        shmemi_fatal ("out of host memory");
+    for (int i = 0; i < k; ++i)
+        for (size_t k0 = 0; k0 < nelems; k0 += piece) {
+            const size_t cnt = nelems - k0 < piece ? nelems - k0 : piece;
+            host_strided_copy (tmp, (const char *) srcs[i] + (ptrdiff_t) k0 * sst * es, (size_t) es, 1, sst, cnt);
+            void *d = (char *) dsts[i] + (ptrdiff_t) k0 * dst * es;
+            if (dst == 1) {
+                SHMEMI_HIP (hipMemcpyAsync (d, tmp, cnt * (size_t) es, hipMemcpyHostToDevice, shmemi.stream));
+            } else {
+                const void *sc = scratch;
+                SHMEMI_HIP (hipMemcpyAsync (scratch, tmp, cnt * (size_t) es, hipMemcpyHostToDevice, shmemi.stream));
+                const int rc = mi355_strided_pull (es, &d, &sc, dst, 1, cnt, 1, shmemi.stream);
+                if (rc != 0)
+                    shmemi_fatal ("%s: strided kernel launch failed: %d", fn, rc);
+            }
+            SHMEMI_HIP (hipStreamSynchronize (shmemi.stream)); /* tmp and scratch are reused */
+        }
+    free (tmp);
+}
+
+/* target_on_m[(i*nelems + k) * dst] = source_on_i[(m*nelems + k) * sst] for
+ * member i < N, k < nelems, m this PE's index IN THE ACTIVE SET.
+ *
+ * Reference: src/alltoall/alltoall.c, alltoall-linear.c:60-84 (one
+ * shmem_iget or shmem_getmem per member, then shmem_quiet). One deliberate
+ * deviation: alltoall-linear.c:74,78 offsets the source by the GLOBAL PE
+ * number (GET_STATE (mype)); that equals the index in the set only for the
+ * set (0, 0, N), and for any other set reads outside the block layout
+ * OpenSHMEM 1.3 defines. This build implements the specification's meaning;
+ * on (0, 0, N) the result is the reference's bit for bit.
+ *
+ * Every member pulls, so the call is bracketed like fcollect_bytes: an
+ * opening barrier (every source is ready) and a closing one (nobody still
+ * reads my source) -- the reference needs neither more than its quiet, its
+ * gets being blocking and its callers synchronising around the call. Small
+ * contiguous calls run as one mi355_fused_pull launch under fcollect's
+ * conditions. */
+static void alltoall_bytes (const char *fn, int es, void *target, const void *source, ptrdiff_t dst, ptrdiff_t sst,
+                            size_t nelems, int PE_start, int logPE_stride, int PE_size)
+{
+    struct cset s = make_set (fn, PE_start, logPE_stride, PE_size);
+    if (dst < 1 || sst < 1)
+        shmemi_fatal ("%s: strides dst %td, sst %td: both must be at least 1", fn, dst, sst);
+    const size_t N = (size_t) s.size, ue = (size_t) es;
+    const size_t sspan = nelems == 0 ? 0 : ((N * nelems - 1) * (size_t) sst + 1) * ue; /* bytes of source read */
+    const int host = source_kind (fn, source, sspan);
+    if (nelems != 0 && target == NULL)
+        shmemi_fatal ("%s: NULL target (%zu elements)", fn, nelems);
+    const int contig = dst == 1 && sst == 1;
+    const size_t nb = nelems * ue;
+    if (!host && contig && s.size >= 2 && s.size <= MI355_PULL_MAX_SEGS && nb != 0 && fused_pull_ok (&s, nb * N)) {
+        size_t toff[MI355_PULL_MAX_SEGS], nbs[MI355_PULL_MAX_SEGS];
+        const void *srcs[MI355_PULL_MAX_SEGS];
+        for (int i = 0; i < s.size; ++i) {
+            toff[i] = (size_t) i * nb;
+            srcs[i] = (const char *) shmemi_peer_ptr (s.start + i * s.stride, shmemi_heap_offset (source)) +
+                      (size_t) s.me * nb;
+            nbs[i] = nb;
+        }
+        SHMEMI_TRACE (SHMEMI_LOG_ALLTOALL, "%s: %d x %zu bytes, one fused launch", fn, s.size, nb);
+        fused_pull (fn, &s, target, nb * N, toff, srcs, nbs, s.size);
+        return;
+    }
+    int dev = 0;
+    if (s.size > 1)
+        dev = collective_entry (fn, source, sspan, &s, 1);
+    else if (!host && nelems != 0)
+        shmemi_order_after_caller (0); /* one member: a local copy, nobody to wait for */
+    if (nelems != 0) {
+        void **dsts = (void **) malloc (sizeof (void *) * N);
+        const void **srcs = (const void **) malloc (sizeof (void *) * N);
+        if (dsts == NULL || srcs == NULL)
+            shmemi_fatal ("out of host memory");
+        for (int i = 0; i < s.size; ++i) {
+            const int pe = s.start + i * s.stride;
+            dsts[i] = (char *) target + (ptrdiff_t) ((size_t) i * nelems) * dst * es;
+            srcs[i] = (const char *) source_on (pe, source, host) + (ptrdiff_t) ((size_t) s.me * nelems) * sst * es;
+        }
+        if (host) {
+            SHMEMI_TRACE (SHMEMI_LOG_ALLTOALL, "%s: %d x %zu elements of %d bytes, strides %td/%td, host", fn, s.size,
+                          nelems, es, dst, sst);
+            a2a_from_host (fn, es, dsts, srcs, dst, sst, nelems, s.size);
+        } else if (is_device_ptr (target)) {
+            SHMEMI_TRACE (SHMEMI_LOG_ALLTOALL, "%s: %d x %zu elements of %d bytes, strides %td/%td, %s kernel", fn,
+                          s.size, nelems, es, dst, sst, contig ? "copy" : "strided");
+            a2a_launch (fn, es, dsts, srcs, dst, sst, nelems, s.size, !dev);
+        } else if (contig) {
+            SHMEMI_TRACE (SHMEMI_LOG_ALLTOALL, "%s: %d x %zu bytes into host memory, copies", fn, s.size, nb);
+            size_t *nbs = (size_t *) malloc (sizeof (size_t) * N);
+            if (nbs == NULL)
+                shmemi_fatal ("out of host memory");
+            for (int i = 0; i < s.size; ++i)
+                nbs[i] = nb;
+            pull_impl (dsts, srcs, nbs, s.size, !dev);
+            free (nbs);
+        } else {
+            SHMEMI_TRACE (SHMEMI_LOG_ALLTOALL,
+                          "%s: %d x %zu elements of %d bytes, strides %td/%td, strided kernel staged into host memory",
+                          fn, s.size, nelems, es, dst, sst);
+            a2a_staged (fn, es, dsts, srcs, dst, sst, nelems, s.size);
+        }
+        free (srcs);
+        free (dsts);
+    }
+    if (s.size > 1)
+        collective_exit (&s, dev); /* nobody reads our source any more */
+}
+
+void pshmem_alltoall32 (void *target, const void *source, size_t nelems, int PE_start, int logPE_stride,
+                        int PE_size, long *pSync)
+{
+    (void) pSync;
+    alltoall_bytes ("shmem_alltoall32", 4, target, source, 1, 1, nelems, PE_start, logPE_stride, PE_size);
+}
+
+void pshmem_alltoall64 (void *target, const void *source, size_t nelems, int PE_start, int logPE_stride,
+                        int PE_size, long *pSync)
+{
+    (void) pSync;
+    alltoall_bytes ("shmem_alltoall64", 8, target, source, 1, 1, nelems, PE_start, logPE_stride, PE_size);
+}
+
+void pshmem_alltoalls32 (void *target, const void *source, ptrdiff_t dst, ptrdiff_t sst, size_t nelems,
+                         int PE_start, int logPE_stride, int PE_size, long *pSync)
+{
+    (void) pSync;
+    alltoall_bytes ("shmem_alltoalls32", 4, target, source, dst, sst, nelems, PE_start, logPE_stride, PE_size);
+}
+
+void pshmem_alltoalls64 (void *target, const void *source, ptrdiff_t dst, ptrdiff_t sst, size_t nelems,
+                         int PE_start, int logPE_stride, int PE_size, long *pSync)
+{
+    (void) pSync;
+    alltoall_bytes ("shmem_alltoalls64", 8, target, source, dst, sst, nelems, PE_start, logPE_stride, PE_size);
+}
+
 #define WEAK(name) __attribute__ ((weak, alias ("p" #name)))
 void shmem_putmem (void *dest, const void *src, size_t nelems, int pe) WEAK (shmem_putmem);
 void shmem_getmem (void *dest, const void *src, size_t nelems, int pe) WEAK (shmem_getmem);
@@ -597,3 +846,11 @@ void shmem_collect32 (void *target, const void *source, size_t nelems, int PE_st
                       int PE_size, long *pSync) WEAK (shmem_collect32);
 void shmem_collect64 (void *target, const void *source, size_t nelems, int PE_start, int logPE_stride,
                       int PE_size, long *pSync) WEAK (shmem_collect64);
+void shmem_alltoall32 (void *target, const void *source, size_t nelems, int PE_start, int logPE_stride,
+                       int PE_size, long *pSync) WEAK (shmem_alltoall32);
+void shmem_alltoall64 (void *target, const void *source, size_t nelems, int PE_start, int logPE_stride,
+                       int PE_size, long *pSync) WEAK (shmem_alltoall64);
+void shmem_alltoalls32 (void *target, const void *source, ptrdiff_t dst, ptrdiff_t sst, size_t nelems,
+                        int PE_start, int logPE_stride, int PE_size, long *pSync) WEAK (shmem_alltoalls32);
+void shmem_alltoalls64 (void *target, const void *source, ptrdiff_t dst, ptrdiff_t sst, size_t nelems,
+                        int PE_start, int logPE_stride, int PE_size, long *pSync) WEAK (shmem_alltoalls64);

@@ -91,3 +91,37 @@ F_LOGIC (F_REDUCTION, or)
 F_LOGIC (F_REDUCTION, xor)
 F_COMPLEX (F_REDUCTION, sum)
 F_COMPLEX (F_REDUCTION, prod)
+
+/* ---- all-to-all (reference src/fortran/fortran.c:1272-1321) ------------ */
+
+void pshmem_alltoall32_ (void *target, const void *source, int *nelems, int *PE_start, int *logPE_stride,
+                         int *PE_size, int *pSync)
+{
+    pshmem_alltoall32 (target, source, (size_t) *nelems, *PE_start, *logPE_stride, *PE_size, (long *) pSync);
+}
+void pshmem_alltoall64_ (void *target, const void *source, int *nelems, int *PE_start, int *logPE_stride,
+                         int *PE_size, int *pSync)
+{
+    pshmem_alltoall64 (target, source, (size_t) *nelems, *PE_start, *logPE_stride, *PE_size, (long *) pSync);
+}
+void pshmem_alltoalls32_ (void *target, const void *source, ptrdiff_t *dst, ptrdiff_t *sst, int *nelems,
+                          int *PE_start, int *logPE_stride, int *PE_size, int *pSync)
+{
+    pshmem_alltoalls32 (target, source, *dst, *sst, (size_t) *nelems, *PE_start, *logPE_stride, *PE_size,
+                        (long *) pSync);
+}
+void pshmem_alltoalls64_ (void *target, const void *source, ptrdiff_t *dst, ptrdiff_t *sst, int *nelems,
+                          int *PE_start, int *logPE_stride, int *PE_size, int *pSync)
+{
+    pshmem_alltoalls64 (target, source, *dst, *sst, (size_t) *nelems, *PE_start, *logPE_stride, *PE_size,
+                        (long *) pSync);
+}
+
+void shmem_alltoall32_ (void *target, const void *source, int *nelems, int *PE_start, int *logPE_stride,
+                        int *PE_size, int *pSync) WEAK_F (shmem_alltoall32_);
+void shmem_alltoall64_ (void *target, const void *source, int *nelems, int *PE_start, int *logPE_stride,
+                        int *PE_size, int *pSync) WEAK_F (shmem_alltoall64_);
+void shmem_alltoalls32_ (void *target, const void *source, ptrdiff_t *dst, ptrdiff_t *sst, int *nelems,
+                         int *PE_start, int *logPE_stride, int *PE_size, int *pSync) WEAK_F (shmem_alltoalls32_);
+void shmem_alltoalls64_ (void *target, const void *source, ptrdiff_t *dst, ptrdiff_t *sst, int *nelems,
+                         int *PE_start, int *logPE_stride, int *PE_size, int *pSync) WEAK_F (shmem_alltoalls64_);

@@ -315,7 +315,7 @@ void shmemi_ext_finalize (void);
 enum shmemi_log_level {
     SHMEMI_LOG_DEBUG = 1, SHMEMI_LOG_INFO, SHMEMI_LOG_VERSION, SHMEMI_LOG_INIT, SHMEMI_LOG_FINALIZE,
     SHMEMI_LOG_BARRIER, SHMEMI_LOG_BROADCAST, SHMEMI_LOG_REDUCTION, SHMEMI_LOG_COLLECT, SHMEMI_LOG_QUIET,
-    SHMEMI_LOG_MEMORY, SHMEMI_LOG_NOTICE, SHMEMI_LOG_NLEVELS
+    SHMEMI_LOG_MEMORY, SHMEMI_LOG_NOTICE, SHMEMI_LOG_ALLTOALL, SHMEMI_LOG_NLEVELS
 };
 #define SHMEMX_VERSION_STRING "osss-gasnet MI355X reduction path (OpenSHMEM 1.3 API, gfx950)"
 extern unsigned shmemi_trace_mask;

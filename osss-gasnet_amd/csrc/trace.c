@@ -34,6 +34,7 @@ static const char *const level_names[SHMEMI_LOG_NLEVELS] = {
     [SHMEMI_LOG_BROADCAST] = "BROADCAST", [SHMEMI_LOG_REDUCTION] = "REDUCTION",
     [SHMEMI_LOG_COLLECT] = "COLLECT",     [SHMEMI_LOG_QUIET] = "QUIET",
     [SHMEMI_LOG_MEMORY] = "MEMORY",       [SHMEMI_LOG_NOTICE] = "NOTICE",
+    [SHMEMI_LOG_ALLTOALL] = "ALLTOALL",
 };
 
 static double mono_s (void)

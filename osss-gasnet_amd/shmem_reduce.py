@@ -37,6 +37,7 @@ SHMEM_SYNC_VALUE = -1
 _vp = ctypes.c_void_p
 _sz = ctypes.c_size_t
 _i = ctypes.c_int
+_pd = ctypes.c_ssize_t  # ptrdiff_t
 
 
 class CallInfo(ctypes.Structure):
@@ -239,6 +240,72 @@ class Shmem:
         if dtype is None:
             raise TypeError(f"no shmem_*_to_all for {source.dtype}")
         self.to_all(op, dtype, target.data_ptr(), source.data_ptr(), source.numel(), PE_start, logPE_stride, PE_size)
+
+    # ---- all-to-all (include/shmem.h)
+    def _alltoall_fn(self, bits, strided):
+        if bits not in (32, 64):
+            raise ValueError("bits must be 32 or 64")
+        name = f"shmem_alltoall{'s' if strided else ''}{bits}"
+        f = self._fns.get(name)
+        if f is None:
+            f = getattr(self.lib, name)
+            f.restype = None
+            f.argtypes = ([_vp, _vp, _pd, _pd, _sz, _i, _i, _i, _vp] if strided
+                          else [_vp, _vp, _sz, _i, _i, _i, _vp])
+            self._fns[name] = f
+        return f
+
+    def alltoall(self, bits, target, source, nelems, PE_start=0, logPE_stride=0, PE_size=None):
+        """shmem_alltoall32/64: block m of member i's source becomes block i of
+        member m's target (nelems elements of bits/8 bytes per block)"""
+        if PE_size is None:
+            PE_size = self.n_pes()
+        self._alltoall_fn(bits, False)(target, source, nelems, PE_start, logPE_stride, PE_size, self._psync_ptr)
+
+    def alltoalls(self, bits, target, source, dst, sst, nelems, PE_start=0, logPE_stride=0, PE_size=None):
+        """shmem_alltoalls32/64: the same with the elements dst apart in the
+        target and sst apart in the source (in elements, both >= 1)"""
+        if PE_size is None:
+            PE_size = self.n_pes()
+        self._alltoall_fn(bits, True)(target, source, dst, sst, nelems, PE_start, logPE_stride, PE_size,
+                                      self._psync_ptr)
+
+    def alltoall_tensors(self, out, x, PE_start=0, logPE_stride=0, PE_size=None):
+        """All-to-all of two contiguous tensors: x (a heap_tensor) is cut into
+        PE_size equal blocks, block m goes to member m; out (any device tensor
+        of the same total bytes) receives member i's block as its block i.
+        Moved as 64-bit elements when a block is a multiple of 8 bytes, as
+        32-bit ones when a multiple of 4; any other block size: ValueError.
+        Blocking, like the C call."""
+        if PE_size is None:
+            PE_size = self.n_pes()
+        total = x.numel() * x.element_size()
+        if out.numel() * out.element_size() != total:
+            raise ValueError("out and x must hold the same number of bytes")
+        if PE_size < 1 or total % PE_size != 0:
+            raise ValueError(f"{total} bytes do not divide into {PE_size} blocks")
+        block = total // PE_size
+        if block % 8 == 0:
+            bits = 64
+        elif block % 4 == 0:
+            bits = 32
+        else:
+            raise ValueError(f"the per-peer block of {block} bytes is not a multiple of 4 bytes")
+        if not (out.is_contiguous() and x.is_contiguous()) or out.device.type != "cuda" or x.device.type != "cuda":
+            raise ValueError("out and x must be contiguous GPU tensors")
+        self.alltoall(bits, out.data_ptr(), x.data_ptr(), block // (bits // 8), PE_start, logPE_stride, PE_size)
+
+    def strided_pull(self, elem_size, dsts, srcs, dst_stride, src_stride, nelems, stream=None):
+        """mi355_strided_pull: dsts[i][k * dst_stride] = srcs[i][k * src_stride], k < nelems"""
+        f = self._fns.get("mi355_strided_pull")
+        if f is None:
+            f = self.lib.mi355_strided_pull
+            f.restype = _i
+            f.argtypes = [_i, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _pd, _pd, _sz, _i, _vp]
+            self._fns["mi355_strided_pull"] = f
+        d = (_vp * len(dsts))(*dsts)
+        s = (_vp * len(srcs))(*srcs)
+        return f(elem_size, d, s, dst_stride, src_stride, nelems, len(dsts), stream)
 
     def heap_tensor(self, n, dtype):
         """A 1-D torch tensor of n elements of torch dtype `dtype` in the
