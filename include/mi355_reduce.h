@@ -92,6 +92,21 @@ int mi355_combine_orders (int op, int dtype, void *const *dsts, const void *cons
 int mi355_copy_segments (void *const *dsts, const void *const *srcs,
                          const size_t *nbytes, int nseg, void *stream);
 
+/* A launch of ONE segment (the 1-PE identity copy, mi355_combine with one
+ * source) sweeps its vectors upward or downward: whole 128-byte lines,
+ * ascending inside each grid pass, the passes taken first to last or last to
+ * first. Each such launch of the process takes the opposite direction to the
+ * previous one, so a pair copied call after call is re-read from the end
+ * touched last, part of which the Infinity Cache still holds. The bytes
+ * written are the same either way. Launches of several segments ascend.
+ *
+ * mi355_copy_direction_next_launch pins the NEXT mi355_copy_segments call of
+ * the calling thread instead: dir > 0 ascending, dir < 0 descending, 0
+ * cancels. For tests and measurement tools; the library never calls it. The
+ * call consumes the request whether or not it launches one segment; error
+ * returns of this layer cancel it. */
+void mi355_copy_direction_next_launch (int dir);
+
 /* nseg independent strided blocks in ONE launch (shmem_alltoalls):
  *   dsts[i][k * dst_stride] = srcs[i][k * src_stride]    for k < nelems
  * with elements of elem_size 4 or 8 bytes and strides in elements, >= 1.

@@ -38,14 +38,22 @@
 namespace mi355k {
 
 // Byte copy of up to NS segments in one launch; blockIdx.y = segment. NS = 1
-// (the 1-PE identity, the bench's call) keeps the kernel arguments at 48
+// (the 1-PE identity, the bench's call) keeps the kernel arguments at 64
 // bytes instead of 1.5 KiB for the 64-segment form (the all-gather leg).
 constexpr int kMaxSeg = 64;
+// step, first: the vector loop's sweep, per launch (seg_sweep). Ascending:
+// first = 0 and step = the grid's vectors per pass; descending (single-segment
+// launches only): first = the last pass's offset and step negative, so the
+// passes run from the last to the first while every pass keeps its ascending
+// whole-line addresses. Every access is guarded by `i < nvec` whatever the
+// two hold.
 template <int NS>
 struct SegParams {
     void *dst[NS];
     const void *src[NS];
     uint64_t nbytes[NS];
+    int64_t step;
+    uint64_t first;
     Signal sig;
 };
 
@@ -70,6 +78,11 @@ __global__ __launch_bounds__(kBlock) void copy_segments(SegParams<NS> p) {
     const uint64_t nb = p.nbytes[sg];
     const char *src = (const char *)p.src[sg];
     char *dst = (char *)p.dst[sg];
+    // the sweep, fetched with the pointers above: left to the compiler, its
+    // scalar load sat behind the first wait, a second round trip before the
+    // wave's first vector load
+    uint64_t step = (uint64_t)p.step, first = p.first;
+    asm volatile("" : "+s"(step), "+s"(first));
     // 16-byte vectors where both ends are aligned: pointers with the same
     // misalignment within 16 bytes (a user offset into two arrays) peel a
     // head so that the target starts on a 128-byte line (seg_plan); different
@@ -85,11 +98,14 @@ __global__ __launch_bounds__(kBlock) void copy_segments(SegParams<NS> p) {
         const u32x4 *s = (const u32x4 *)(src + head);
         u32x4 *d = (u32x4 *)(dst + head);
         const uint64_t nvec = (nb - head) / 16;
-        const uint64_t step = (uint64_t)gridDim.x * kBlock * UNROLL;
+        // step is signed, modulo 2^64: a descending sweep ends when base
+        // passes below the first pass and wraps above nvec
         // software-pipelined: the loads of pass k+1 are in flight while the
         // stores of pass k issue (tools/probes/copy_variants.hip: 78.3 vs 80.0 us for
         // 256 MiB at UNROLL 4, one block per CU, over all-loads-then-stores)
-        uint64_t base = (uint64_t)blockIdx.x * kBlock * UNROLL + threadIdx.x;
+        uint64_t base = first + (uint64_t)blockIdx.x * kBlock * UNROLL + threadIdx.x;
+        // descending: a lane with nothing in the (partial) last pass starts one pass down
+        if (base >= nvec) base += step;
         u32x4 x[UNROLL];
 #pragma unroll
         for (int u = 0; u < UNROLL; ++u) {
@@ -169,8 +185,11 @@ __global__ __launch_bounds__(kBlock) void copy_segments_shift(SegParams<NS> p) {
     // copy_segments' pipelined loop, two blocks per CU (cold_probe linepeel,
     // 256 MiB: 77 us = 0.87 of peak, 87 us before the target was peeled to
     // its line; one vector per lane per pass: 119 us)
-    const uint64_t step = (uint64_t)gridDim.x * kBlock * UNROLL;
-    uint64_t base = (uint64_t)blockIdx.x * kBlock * UNROLL + threadIdx.x;
+    // signed, ascending or descending, and fetched with the pointers, as copy_segments
+    uint64_t step = (uint64_t)p.step, first = p.first;
+    asm volatile("" : "+s"(step), "+s"(first));
+    uint64_t base = first + (uint64_t)blockIdx.x * kBlock * UNROLL + threadIdx.x;
+    if (base >= nvec) base += step;
     u32x4 x[UNROLL];
 #pragma unroll
     for (int u = 0; u < UNROLL; ++u) {
@@ -326,7 +345,11 @@ static int copy_segments_impl(void *const *dsts, const void *const *srcs, const 
 static int combine_orders_impl(int op, int dtype, void *const *dsts, const void *const *srcs, int nsrc, size_t n,
                                void *stream);
 
-// Every error return cancels an armed signal/timing request (nothing carries them).
+// mi355_copy_direction_next_launch: > 0 ascending, < 0 descending, 0: none
+// (single-segment copies alternate, next_copy_descends)
+static thread_local int t_copy_dir = 0;
+
+// Every error return cancels an armed signal/timing/direction request (nothing carries them).
 extern "C" int mi355_combine(int op, int dtype, void *dst, const void *const *srcs, int nsrc,
                              size_t n, void *stream) {
     const int rc = combine_impl(op, dtype, dst, srcs, nsrc, n, stream);
@@ -334,6 +357,7 @@ extern "C" int mi355_combine(int op, int dtype, void *dst, const void *const *sr
     if (rc != 0) {
         t_sig = Signal{nullptr, nullptr, 0};
         t_ev_start = t_ev_stop = nullptr;
+        t_copy_dir = 0;
     }
     return rc;
 }
@@ -344,6 +368,7 @@ extern "C" int mi355_combine_orders(int op, int dtype, void *const *dsts, const 
     if (rc != 0) {
         t_sig = Signal{nullptr, nullptr, 0};
         t_ev_start = t_ev_stop = nullptr;
+        t_copy_dir = 0;
     }
     return rc;
 }
@@ -351,6 +376,7 @@ extern "C" int mi355_combine_orders(int op, int dtype, void *const *dsts, const 
 extern "C" int mi355_copy_segments(void *const *dsts, const void *const *srcs, const size_t *nbytes,
                                    int nseg, void *stream) {
     const int rc = copy_segments_impl(dsts, srcs, nbytes, nseg, stream);
+    t_copy_dir = 0;  // a multi-segment launch (always ascending) or a call with nothing to copy consumes it too
     if (rc != 0) {
         t_sig = Signal{nullptr, nullptr, 0};
         t_ev_start = t_ev_stop = nullptr;
@@ -423,6 +449,39 @@ static int combine_orders_impl(int op, int dtype, void *const *dsts, const void 
     }
 }
 
+// The sweep direction of single-segment copies (the 1-PE identity, blocking
+// or on a stream, and the overlap path's two copies through scratch). The
+// same pair copied call after call is 2 S of traffic per call, twice the
+// Infinity Cache at the headline's 256 MiB: swept upward every time, each
+// line's reuse distance is the whole 2 S. Turning round at the end of each
+// call leaves the lines touched last to be touched first by the next call
+// ("The copy's sweep direction"). Each such launch takes the
+// opposite direction to the process's previous one (several threads may
+// launch: a relaxed atomic; the first launch ascends), unless
+// mi355_copy_direction_next_launch pinned this thread's next launch.
+static std::atomic<unsigned> g_copy_descended{1};
+
+static bool next_copy_descends() {
+    const int pin = t_copy_dir;
+    t_copy_dir = 0;
+    if (pin != 0) {
+        g_copy_descended.store(pin < 0 ? 1u : 0u, std::memory_order_relaxed);
+        return pin < 0;
+    }
+    return (g_copy_descended.fetch_xor(1u, std::memory_order_relaxed) & 1u) == 0;
+}
+
+// A single-segment launch's step and first pass (SegParams), `pass` vectors per grid pass.
+static void seg_sweep(SegParams<1> &p, uint64_t pass, bool descending) {
+    p.step = (int64_t)pass;
+    p.first = 0;
+    if (!descending) return;
+    const uint64_t nvec = (p.nbytes[0] - seg_plan(p.dst[0], p.src[0], p.nbytes[0]).head) / 16;
+    const uint64_t npass = (nvec + pass - 1) / pass;
+    p.step = -(int64_t)pass;
+    p.first = npass > 0 ? (npass - 1) * pass : 0;
+}
+
 static int copy_segments_impl(void *const *dsts, const void *const *srcs, const size_t *nbytes, int nseg,
                               void *stream) {
     if (nseg < 0 || nseg > kMaxSeg) return MI355_E_INVAL;
@@ -460,16 +519,24 @@ static int copy_segments_impl(void *const *dsts, const void *const *srcs, const 
     // keep total blocks ~ cap when many segments share the chip
     unsigned cap = (unsigned)device_cus() * (shifted ? 2 : 1);
     if ((uint64_t)gx * used > cap) gx = cap / used > 0 ? cap / used : 1;
+    const uint64_t pass = (uint64_t)gx * kBlock * U;   // vectors per grid pass
     if (used == 1) {
         SegParams<1> p1{};
         p1.dst[0] = p.dst[0];
         p1.src[0] = p.src[0];
         p1.nbytes[0] = p.nbytes[0];
+        seg_sweep(p1, pass, next_copy_descends());
         return launch(shifted ? copy_segments_shift<U, 1> : copy_segments<U, 1>, dim3(gx, 1), (hipStream_t)stream, p1);
     }
+    // several segments (the all-gather leg, fcollect): ascending, their sources
+    // are peers' memory, which this GPU's Infinity Cache does not hold
+    p.step = (int64_t)pass;
+    p.first = 0;
     return launch(shifted ? copy_segments_shift<U, kMaxSeg> : copy_segments<U, kMaxSeg>, dim3(gx, used),
                   (hipStream_t)stream, p);
 }
+
+extern "C" void mi355_copy_direction_next_launch(int dir) { t_copy_dir = dir; }
 
 extern "C" void mi355_nan_flag_next_launch(unsigned long long *set, unsigned long long *clear) {
     t_nan_set = set;

@@ -85,6 +85,7 @@ def load(path=LIB_PATH):
         "mi355_combine": ([_i, _i, _vp, ctypes.POINTER(_vp), _i, _sz, _vp], _i),
         "mi355_combine_orders": ([_i, _i, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _i, _sz, _vp], _i),
         "mi355_copy_segments": ([ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_sz), _i, _vp], _i),
+        "mi355_copy_direction_next_launch": ([_i], None),
         "mi355_shard_bounds": ([_sz, _sz, _i, _i, ctypes.POINTER(_sz), ctypes.POINTER(_sz)], None),
     }
     for name, (args, res) in sig.items():
