@@ -155,6 +155,16 @@ void mi355_signal_next_launch (unsigned *count, unsigned *flag, unsigned epoch);
 const void *mi355_last_kernel (void);
 int mi355_kernel_name (const void *kernel, char *buf, size_t len);
 
+/* What the tests of the grid-stride loops observe ("Grid
+ * passes"). mi355_device_cus: the compute units of the current GPU as this
+ * layer's launchers count them when they cap a grid (256 when the device
+ * cannot be queried). mi355_last_launch_grid: the grid (blocks in x and y) of
+ * the kernel this layer launched last from the calling thread through its
+ * launch helper -- every fold, copy, patch copy and strided pull; 0, 0 before
+ * the first. Read-only, never used by the library itself. */
+int mi355_device_cus (void);
+void mi355_last_launch_grid (unsigned *gx, unsigned *gy);
+
 /* Launch a one-block kernel whose only job is to carry the armed signal:
  * the host learns that everything queued on `stream` before it is done. */
 int mi355_signal_launch (void *stream);

@@ -642,6 +642,13 @@ extern "C" void mi355i_note_launch(const void *kernel) { t_last_kernel = kernel;
 
 extern "C" const void *mi355_last_kernel(void) { return t_last_kernel; }
 
+extern "C" int mi355_device_cus(void) { return device_cus(); }
+
+extern "C" void mi355_last_launch_grid(unsigned *gx, unsigned *gy) {
+    if (gx != nullptr) *gx = t_last_grid[0];
+    if (gy != nullptr) *gy = t_last_grid[1];
+}
+
 // The kernel's demangled name, as rocprofv3 prints it ("void
 // mi355k::copy_segments<4, 1>(mi355k::SegParams<1>)"). Not on the hot path:
 // the runtime keeps the stub pointer per call and resolves it on request.

@@ -554,6 +554,8 @@ inline thread_local hipEvent_t t_ev_start = nullptr, t_ev_stop = nullptr;
 inline thread_local Signal t_sig = {nullptr, nullptr, 0};
 // host stub of the kernel this layer launched last (mi355_last_kernel)
 inline thread_local const void *t_last_kernel = nullptr;
+// ... and its grid (mi355_last_launch_grid)
+inline thread_local unsigned t_last_grid[2] = {0, 0};
 // NaN words for the next fold (mi355_nan_flag_next_launch), consumed by it
 inline thread_local unsigned long long *t_nan_set = nullptr, *t_nan_clear = nullptr;
 
@@ -575,6 +577,7 @@ int launch(K kernel, dim3 grid, hipStream_t st, P p, bool final = true) {
         t_sig = Signal{nullptr, nullptr, 0};
     }
     t_last_kernel = (const void *)kernel;
+    t_last_grid[0] = grid.x, t_last_grid[1] = grid.y;
     if (t_ev_start != nullptr || t_ev_stop != nullptr) {
         hipExtLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, st, t_ev_start, t_ev_stop, 0, p);
         t_ev_start = t_ev_stop = nullptr;

@@ -86,6 +86,9 @@ def load(path=LIB_PATH):
         "mi355_combine_orders": ([_i, _i, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _i, _sz, _vp], _i),
         "mi355_copy_segments": ([ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_sz), _i, _vp], _i),
         "mi355_copy_direction_next_launch": ([_i], None),
+        "mi355_device_cus": ([], _i),
+        "mi355_last_launch_grid": ([ctypes.POINTER(ctypes.c_uint)] * 2, None),
+        "mi355_nan_patch_copy": ([_i, _vp, _vp, _vp, _sz, _vp, _vp], _i),
         "mi355_shard_bounds": ([_sz, _sz, _i, _i, ctypes.POINTER(_sz), ctypes.POINTER(_sz)], None),
     }
     for name, (args, res) in sig.items():
@@ -394,6 +397,17 @@ class Shmem:
         d = (_vp * len(dsts))(*[x if x else None for x in dsts])
         s = (_vp * len(srcs))(*srcs)
         return self.lib.mi355_combine_orders(OPS.index(op), DTYPES.index(dtype), d, s, len(srcs), n, stream)
+
+    def device_cus(self):
+        """mi355_device_cus: the CU count the launchers cap their grids with"""
+        return int(self.lib.mi355_device_cus())
+
+    def last_launch_grid(self):
+        """(gx, gy) of the kernel the combine layer launched last from this
+        thread (mi355_last_launch_grid); (0, 0) before the first launch"""
+        gx, gy = ctypes.c_uint(), ctypes.c_uint()
+        self.lib.mi355_last_launch_grid(ctypes.byref(gx), ctypes.byref(gy))
+        return gx.value, gy.value
 
     def last_call_info(self):
         """dict of shmemx_last_call_info, or None before the first call"""

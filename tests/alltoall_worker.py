@@ -7,7 +7,8 @@ usage: alltoall_worker.py SPEC.json OUTDIR   (identity from SHMEM_PE / SHMEM_NPE
 A case: {"id", "kind": alltoall | alltoalls | fcollect | sum, "bits", "n",
 "dst", "sst", "sets", "target": device | host | pageable | mixed, "source":
 device | host, "seed", "slen", "tlen"}; slen / tlen are the elements of the
-source filled and of the target read back (sentinel -7 first).
+source filled and of the target read back (sentinel -7 first). "report_grid":
+also save mi355_last_launch_grid after the call, as "grid<id>".
 """
 import ctypes
 import json
@@ -78,6 +79,9 @@ def run_case(shm, c, me, bufs, results):
         shm.to_all("sum", "int", tgt, src, n, *mine)
     else:
         raise ValueError(kind)
+    if c.get("report_grid"):
+        # the grid of the strided kernel this PE just launched (the test's pass rule)
+        results[f"grid{c['id']}"] = np.array(shm.last_launch_grid())
     if kt == "device":
         got = shm.get(tgt, tlen, dt)
     else:
@@ -93,11 +97,15 @@ def main():
     shm.init()
     me = shm.my_pe()
     cases = spec["cases"]
-    smax = max([c["slen"] for c in cases] + [1]) * 8 + 64
-    tmax = max([c["tlen"] for c in cases] + [1]) * 8 + 64
+    def most(key, where=lambda c: True):
+        """bytes of the largest source (slen) or target (tlen) among the cases `where` picks"""
+        return max([c[key] * c["bits"] // 8 for c in cases if where(c)] + [8]) + 64
+
     off = spec.get("offset", 0)  # bytes off the allocations' alignment, both symmetric
-    bufs = {"da": shm.malloc_device(smax) + off, "db": shm.malloc_device(tmax) + off,
-            "ha": shm.malloc(smax) + off, "hb": shm.malloc(tmax) + off}
+    # the host-heap buffers only as large as the cases that use them
+    bufs = {"da": shm.malloc_device(most("slen")) + off, "db": shm.malloc_device(most("tlen")) + off,
+            "ha": shm.malloc(most("slen", lambda c: c.get("source", "device") == "host")) + off,
+            "hb": shm.malloc(most("tlen", lambda c: c.get("target", "device") == "host")) + off}
     assert all(v > off for v in bufs.values()), bufs
     results = {}
     for c in cases:

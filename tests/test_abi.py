@@ -85,6 +85,20 @@ def test_shard_bounds_partition():
                 assert prev == n
 
 
+def test_launch_grid_queries_before_any_launch():
+    """mi355_last_launch_grid reads 0, 0 in a thread that has launched nothing
+    (this process never launches: there is no GPU here), null outputs are
+    allowed, and mi355_device_cus is positive even when no device can be
+    queried (the launchers' fallback)."""
+    s = shmem_reduce.Shmem()   # loads the library; no shmem_init
+    assert s.last_launch_grid() == (0, 0)
+    gx = ctypes.c_uint(77)
+    s.lib.mi355_last_launch_grid(ctypes.byref(gx), None)
+    s.lib.mi355_last_launch_grid(None, None)
+    assert gx.value == 0
+    assert s.device_cus() > 0
+
+
 def test_constants_match_reference_values():
     text = open(os.path.join(ROOT, "include", "shmem.h")).read()
     assert "#define SHMEM_REDUCE_SYNC_SIZE          (256L / SHMEM_INTERNAL_F2C_SCALE)" in text

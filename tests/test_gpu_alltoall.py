@@ -59,6 +59,24 @@ def test_strided_pull_kernel(kernel_results, es, nseg):
     assert not failures, failures
 
 
+def passes_rule(gx, nelems):
+    """at least two full grid passes and a partial one, whatever the kernel's
+    per-lane unroll (4 at most); from the grid the library reported"""
+    return gx > 0 and nelems > 2 * 4 * 256 * gx
+
+
+@pytest.mark.parametrize("es,nseg", [(4, 64), (8, 64), (8, 1)])
+def test_strided_pull_kernel_past_one_pass(kernel_results, es, nseg):
+    """Strides (1,2) (1,3) (2,1) (3,1) (2,3) (3,2) at 9 * 1024 * gx + 1024 + 37
+    elements per segment, gx read back from the library: every block takes
+    several trips round its tile loop and the last one is partial."""
+    failures = kernel_results["passes"][f"{es}-{nseg}"]
+    info = kernel_results["passes_info"][f"{es}-{nseg}"]
+    print(f"grid-pass | strided_pull es {es} x{nseg} | (strides, gx, gy, nelems) {info}")
+    assert not failures, failures
+    assert len(info) == 6 and all(passes_rule(gx, n) and gy == nseg for _, gx, gy, n in info), info
+
+
 def test_strided_pull_rejects_bad_arguments(kernel_results):
     rec = kernel_results["bad_arguments"]
     assert all(rc != 0 for rc in rec["rcs"]) and rec["untouched"], rec
@@ -100,7 +118,7 @@ def run_a2a(npes, cases, tmp_path, extra_env=None, timeout=300, offset=0):
     return [np.load(tmp_path / f"pe{pe}.npz") for pe in range(npes)]
 
 
-def case(cid, kind, bits, n, sets, dst=1, sst=1, target="device", source="device", seed=None):
+def case(cid, kind, bits, n, sets, dst=1, sst=1, target="device", source="device", seed=None, report_grid=False):
     big = max(s[2] for s in sets)
     if kind in ("alltoall", "alltoalls"):
         slen = (big * n - 1) * sst + 1 if n else 0
@@ -110,7 +128,8 @@ def case(cid, kind, bits, n, sets, dst=1, sst=1, target="device", source="device
     else:
         slen, tlen = n, n + 5
     return {"id": cid, "kind": kind, "bits": bits, "n": n, "sets": sets, "dst": dst, "sst": sst, "target": target,
-            "source": source, "seed": 5000 + cid if seed is None else seed, "slen": slen, "tlen": tlen}
+            "source": source, "seed": 5000 + cid if seed is None else seed, "slen": slen, "tlen": tlen,
+            "report_grid": report_grid}
 
 
 @functools.lru_cache(maxsize=None)
@@ -161,12 +180,16 @@ FOUR_SETS = [[[0, 0, 4]], [[0, 1, 2], [1, 1, 2]], [[1, 0, 3]], [[2, 0, 1], [3, 0
 
 @pytest.mark.multipe
 @pytest.mark.parametrize("fused", ["default", "0"], ids=["fused", "copy-kernel"])
-def test_alltoall_four_pes(tmp_path, fused):
+def test_alltoall_four_pes(tmp_path, fused, kernel_results):
     """Small contiguous calls run as one fused pull launch by default;
     SHMEM_FUSED_MAX_BYTES=0 sends every one through barrier + copy kernel +
     barrier. The strided calls run barrier + strided kernel + barrier either
     way (a host target: staged through scratch, 384 KiB here, so the larger
-    cases take several passes)."""
+    cases take several passes). With the default thresholds, two more strided
+    calls into device memory large enough for every block of the 4-segment
+    launch to pass several times over its share (sized from the grid the
+    kernel process saw for 4 segments; each PE reports the grid it launched
+    and the rule is asserted from that)."""
     cases, cid = [], 0
     pairs = []
     for bits in (32, 64):
@@ -191,8 +214,23 @@ def test_alltoall_four_pes(tmp_path, fused):
                 cases += [a, b]
                 pairs.append((a["id"], b["id"]))
     extra = {} if fused == "default" else {"SHMEM_FUSED_MAX_BYTES": fused}
+    large = []
+    if fused == "default":   # the strided calls take the same path either way: once is enough
+        for dst, sst in ((2, 3), (1, 3)):
+            gx = kernel_results["grid_of_four_segments"][f"{dst},{sst}"]
+            large.append(case(cid, "alltoalls", 32, 9 * 1024 * gx + 1024 + 37, [[0, 0, 4]], dst, sst,
+                              report_grid=True, seed=4242)); cid += 1   # one seed: the PEs' sources are shared
+        cases += large
+        heap = sum(max(c[k] * c["bits"] // 8 for c in cases) for k in ("slen", "tlen"))
+        extra["SHMEM_DEVICE_HEAP_SIZE"] = f"{heap // 2**20 + 32}M"
     res = run_a2a(4, cases, tmp_path, extra_env=extra)
     check(res, cases)
+    for c in large:
+        for pe in range(4):
+            gx, gy = (int(v) for v in res[pe][f"grid{c['id']}"])
+            print(f"grid-pass | alltoalls32 ({c['dst']},{c['sst']}) PE {pe} | {gx} x {gy} | nelems {c['n']}")
+            assert gy == 4 and passes_rule(gx, c["n"]), (c["id"], pe, gx, gy, c["n"])
+    cached_source.cache_clear()
     for a, b in pairs:
         for pe in range(4):
             assert (res[pe][str(a)] == res[pe][str(b)]).all()
