@@ -118,6 +118,15 @@ void mi355_copy_direction_next_launch (int dir);
 int mi355_strided_pull (int elem_size, void *const *dsts, const void *const *srcs,
                         ptrdiff_t dst_stride, ptrdiff_t src_stride, size_t nelems, int nseg, void *stream);
 
+/* The same contract for elem_size 1, 2, 4, 8 or 16 (shmem_iput / shmem_iget;
+ * mi355_strided_pull is its 4- and 8-byte front and launches the same
+ * kernels). 1- and 2-byte elements take the same three forms with 16 and 8
+ * elements per vector. A 16-byte element is a vector already: every lane moves
+ * one element per slot on both sides, whatever the strides (both 1 is still
+ * mi355_copy_segments), and the pointers must be 16-byte aligned. */
+int mi355_strided_copy (int elem_size, void *const *dsts, const void *const *srcs,
+                        ptrdiff_t dst_stride, ptrdiff_t src_stride, size_t nelems, int nseg, void *stream);
+
 /* The two-member all-gather of a float/double sum or product: dst[i] =
  * own[i] quieted where own[i] is a NaN, else peer[i] (the other member's shard,
  * folded in its order: the same bits as this member's order except where

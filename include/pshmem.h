@@ -51,6 +51,60 @@ void pshmem_longlong_get (long long *dest, const long long *src, size_t nelems, 
 void pshmem_longdouble_get (long double *dest, const long double *src, size_t nelems, int pe);
 void pshmem_double_get (double *dest, const double *src, size_t nelems, int pe);
 void pshmem_float_get (float *dest, const float *src, size_t nelems, int pe);
+void pshmem_char_iput (char *target, const char *source, ptrdiff_t tst, ptrdiff_t sst, size_t nelems,
+                       int pe);
+void pshmem_short_iput (short *target, const short *source, ptrdiff_t tst, ptrdiff_t sst, size_t nelems,
+                        int pe);
+void pshmem_int_iput (int *target, const int *source, ptrdiff_t tst, ptrdiff_t sst, size_t nelems,
+                      int pe);
+void pshmem_long_iput (long *target, const long *source, ptrdiff_t tst, ptrdiff_t sst, size_t nelems,
+                       int pe);
+void pshmem_longlong_iput (long long *target, const long long *source, ptrdiff_t tst, ptrdiff_t sst, size_t nelems,
+                           int pe);
+void pshmem_float_iput (float *target, const float *source, ptrdiff_t tst, ptrdiff_t sst, size_t nelems,
+                        int pe);
+void pshmem_double_iput (double *target, const double *source, ptrdiff_t tst, ptrdiff_t sst, size_t nelems,
+                         int pe);
+void pshmem_longdouble_iput (long double *target, const long double *source, ptrdiff_t tst, ptrdiff_t sst, size_t nelems,
+                             int pe);
+void pshmem_iput32 (void *target, const void *source, ptrdiff_t tst, ptrdiff_t sst, size_t nelems, int pe);
+void pshmem_iput64 (void *target, const void *source, ptrdiff_t tst, ptrdiff_t sst, size_t nelems, int pe);
+void pshmem_iput128 (void *target, const void *source, ptrdiff_t tst, ptrdiff_t sst, size_t nelems, int pe);
+void pshmem_char_iget (char *target, const char *source, ptrdiff_t tst, ptrdiff_t sst, size_t nelems,
+                       int pe);
+void pshmem_short_iget (short *target, const short *source, ptrdiff_t tst, ptrdiff_t sst, size_t nelems,
+                        int pe);
+void pshmem_int_iget (int *target, const int *source, ptrdiff_t tst, ptrdiff_t sst, size_t nelems,
+                      int pe);
+void pshmem_long_iget (long *target, const long *source, ptrdiff_t tst, ptrdiff_t sst, size_t nelems,
+                       int pe);
+void pshmem_longlong_iget (long long *target, const long long *source, ptrdiff_t tst, ptrdiff_t sst, size_t nelems,
+                           int pe);
+void pshmem_float_iget (float *target, const float *source, ptrdiff_t tst, ptrdiff_t sst, size_t nelems,
+                        int pe);
+void pshmem_double_iget (double *target, const double *source, ptrdiff_t tst, ptrdiff_t sst, size_t nelems,
+                         int pe);
+void pshmem_longdouble_iget (long double *target, const long double *source, ptrdiff_t tst, ptrdiff_t sst, size_t nelems,
+                             int pe);
+void pshmem_iget32 (void *target, const void *source, ptrdiff_t tst, ptrdiff_t sst, size_t nelems, int pe);
+void pshmem_iget64 (void *target, const void *source, ptrdiff_t tst, ptrdiff_t sst, size_t nelems, int pe);
+void pshmem_iget128 (void *target, const void *source, ptrdiff_t tst, ptrdiff_t sst, size_t nelems, int pe);
+void pshmem_char_p (char *addr, char value, int pe);
+void pshmem_short_p (short *addr, short value, int pe);
+void pshmem_int_p (int *addr, int value, int pe);
+void pshmem_long_p (long *addr, long value, int pe);
+void pshmem_longlong_p (long long *addr, long long value, int pe);
+void pshmem_float_p (float *addr, float value, int pe);
+void pshmem_double_p (double *addr, double value, int pe);
+void pshmem_longdouble_p (long double *addr, long double value, int pe);
+char pshmem_char_g (char *addr, int pe);
+short pshmem_short_g (short *addr, int pe);
+int pshmem_int_g (int *addr, int pe);
+long pshmem_long_g (long *addr, int pe);
+long long pshmem_longlong_g (long long *addr, int pe);
+float pshmem_float_g (float *addr, int pe);
+double pshmem_double_g (double *addr, int pe);
+long double pshmem_longdouble_g (long double *addr, int pe);
 void pshmem_broadcast64 (void *target, const void *source, size_t nelems, int PE_root, int PE_start,
                          int logPE_stride, int PE_size, long *pSync);
 void pshmem_broadcast32 (void *target, const void *source, size_t nelems, int PE_root, int PE_start,

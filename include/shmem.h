@@ -100,6 +100,66 @@ void shmem_longdouble_get (long double *dest, const long double *src, size_t nel
 void shmem_double_get (double *dest, const double *src, size_t nelems, int pe);
 void shmem_float_get (float *dest, const float *src, size_t nelems, int pe);
 
+/* ---- strided put/get and single elements (reference src/shmem.h:472-560):
+ *      target[k * tst] = source[k * sst] for k < nelems, strides in elements
+ *      and >= 1; the remote side in the device symmetric heap or the
+ *      symmetric host heap. Every other element of the target is left alone.
+ *      Blocking, like put/get. ---- */
+void shmem_char_iput (char *target, const char *source, ptrdiff_t tst, ptrdiff_t sst, size_t nelems,
+                      int pe);
+void shmem_short_iput (short *target, const short *source, ptrdiff_t tst, ptrdiff_t sst, size_t nelems,
+                       int pe);
+void shmem_int_iput (int *target, const int *source, ptrdiff_t tst, ptrdiff_t sst, size_t nelems,
+                     int pe);
+void shmem_long_iput (long *target, const long *source, ptrdiff_t tst, ptrdiff_t sst, size_t nelems,
+                      int pe);
+void shmem_longlong_iput (long long *target, const long long *source, ptrdiff_t tst, ptrdiff_t sst, size_t nelems,
+                          int pe);
+void shmem_float_iput (float *target, const float *source, ptrdiff_t tst, ptrdiff_t sst, size_t nelems,
+                       int pe);
+void shmem_double_iput (double *target, const double *source, ptrdiff_t tst, ptrdiff_t sst, size_t nelems,
+                        int pe);
+void shmem_longdouble_iput (long double *target, const long double *source, ptrdiff_t tst, ptrdiff_t sst, size_t nelems,
+                            int pe);
+void shmem_iput32 (void *target, const void *source, ptrdiff_t tst, ptrdiff_t sst, size_t nelems, int pe);
+void shmem_iput64 (void *target, const void *source, ptrdiff_t tst, ptrdiff_t sst, size_t nelems, int pe);
+void shmem_iput128 (void *target, const void *source, ptrdiff_t tst, ptrdiff_t sst, size_t nelems, int pe);
+void shmem_char_iget (char *target, const char *source, ptrdiff_t tst, ptrdiff_t sst, size_t nelems,
+                      int pe);
+void shmem_short_iget (short *target, const short *source, ptrdiff_t tst, ptrdiff_t sst, size_t nelems,
+                       int pe);
+void shmem_int_iget (int *target, const int *source, ptrdiff_t tst, ptrdiff_t sst, size_t nelems,
+                     int pe);
+void shmem_long_iget (long *target, const long *source, ptrdiff_t tst, ptrdiff_t sst, size_t nelems,
+                      int pe);
+void shmem_longlong_iget (long long *target, const long long *source, ptrdiff_t tst, ptrdiff_t sst, size_t nelems,
+                          int pe);
+void shmem_float_iget (float *target, const float *source, ptrdiff_t tst, ptrdiff_t sst, size_t nelems,
+                       int pe);
+void shmem_double_iget (double *target, const double *source, ptrdiff_t tst, ptrdiff_t sst, size_t nelems,
+                        int pe);
+void shmem_longdouble_iget (long double *target, const long double *source, ptrdiff_t tst, ptrdiff_t sst, size_t nelems,
+                            int pe);
+void shmem_iget32 (void *target, const void *source, ptrdiff_t tst, ptrdiff_t sst, size_t nelems, int pe);
+void shmem_iget64 (void *target, const void *source, ptrdiff_t tst, ptrdiff_t sst, size_t nelems, int pe);
+void shmem_iget128 (void *target, const void *source, ptrdiff_t tst, ptrdiff_t sst, size_t nelems, int pe);
+void shmem_char_p (char *addr, char value, int pe);
+void shmem_short_p (short *addr, short value, int pe);
+void shmem_int_p (int *addr, int value, int pe);
+void shmem_long_p (long *addr, long value, int pe);
+void shmem_longlong_p (long long *addr, long long value, int pe);
+void shmem_float_p (float *addr, float value, int pe);
+void shmem_double_p (double *addr, double value, int pe);
+void shmem_longdouble_p (long double *addr, long double value, int pe);
+char shmem_char_g (char *addr, int pe);
+short shmem_short_g (short *addr, int pe);
+int shmem_int_g (int *addr, int pe);
+long shmem_long_g (long *addr, int pe);
+long long shmem_longlong_g (long long *addr, int pe);
+float shmem_float_g (float *addr, int pe);
+double shmem_double_g (double *addr, int pe);
+long double shmem_longdouble_g (long double *addr, int pe);
+
 /* ---- broadcast / collect (reference src/shmem.h:1746-1779); sources in the
  *      device symmetric heap ---- */
 #define SHMEM_COLLECT_SYNC_SIZE (128L / SHMEM_INTERNAL_F2C_SCALE)

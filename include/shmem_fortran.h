@@ -118,6 +118,31 @@ void shmem_alltoalls32_ (void *target, const void *source, ptrdiff_t *dst, ptrdi
         int *PE_start, int *logPE_stride, int *PE_size, int *pSync);
 void shmem_alltoalls64_ (void *target, const void *source, ptrdiff_t *dst, ptrdiff_t *sst, int *nelems,
         int *PE_start, int *logPE_stride, int *PE_size, int *pSync);
+/* strided put/get (reference src/fortran/fortran.c:482-573): strides and counts
+ * are INTEGERs by reference; element sizes: character 1; integer, logical,
+ * real, 4, 32: 4 bytes; double, complex, 8, 64: 8 bytes; 128: 16 bytes */
+void shmem_character_iput_ (char *target, const char *source, int *tst, int *sst, int *nelems, int *pe);
+void shmem_double_iput_ (double *target, const double *source, int *tst, int *sst, int *nelems, int *pe);
+void shmem_integer_iput_ (int *target, const int *source, int *tst, int *sst, int *nelems, int *pe);
+void shmem_logical_iput_ (int *target, const int *source, int *tst, int *sst, int *nelems, int *pe);
+void shmem_real_iput_ (int *target, const int *source, int *tst, int *sst, int *nelems, int *pe);
+void shmem_complex_iput_ (SHMEM_F_COMPLEX (float) *target, const SHMEM_F_COMPLEX (float) *source, int *tst, int *sst, int *nelems, int *pe);
+void shmem_iput4_ (void *target, const void *source, int *tst, int *sst, int *nelems, int *pe);
+void shmem_iput8_ (void *target, const void *source, int *tst, int *sst, int *nelems, int *pe);
+void shmem_iput32_ (void *target, const void *source, int *tst, int *sst, int *nelems, int *pe);
+void shmem_iput64_ (void *target, const void *source, int *tst, int *sst, int *nelems, int *pe);
+void shmem_iput128_ (void *target, const void *source, int *tst, int *sst, int *nelems, int *pe);
+void shmem_character_iget_ (char *target, const char *source, int *tst, int *sst, int *nelems, int *pe);
+void shmem_double_iget_ (double *target, const double *source, int *tst, int *sst, int *nelems, int *pe);
+void shmem_integer_iget_ (int *target, const int *source, int *tst, int *sst, int *nelems, int *pe);
+void shmem_logical_iget_ (int *target, const int *source, int *tst, int *sst, int *nelems, int *pe);
+void shmem_real_iget_ (int *target, const int *source, int *tst, int *sst, int *nelems, int *pe);
+void shmem_complex_iget_ (SHMEM_F_COMPLEX (float) *target, const SHMEM_F_COMPLEX (float) *source, int *tst, int *sst, int *nelems, int *pe);
+void shmem_iget4_ (void *target, const void *source, int *tst, int *sst, int *nelems, int *pe);
+void shmem_iget8_ (void *target, const void *source, int *tst, int *sst, int *nelems, int *pe);
+void shmem_iget32_ (void *target, const void *source, int *tst, int *sst, int *nelems, int *pe);
+void shmem_iget64_ (void *target, const void *source, int *tst, int *sst, int *nelems, int *pe);
+void shmem_iget128_ (void *target, const void *source, int *tst, int *sst, int *nelems, int *pe);
 
 /* strong (PSHMEM) names */
 void pstart_pes_ (int *npes);
@@ -214,6 +239,28 @@ void pshmem_alltoalls32_ (void *target, const void *source, ptrdiff_t *dst, ptrd
         int *PE_start, int *logPE_stride, int *PE_size, int *pSync);
 void pshmem_alltoalls64_ (void *target, const void *source, ptrdiff_t *dst, ptrdiff_t *sst, int *nelems,
         int *PE_start, int *logPE_stride, int *PE_size, int *pSync);
+void pshmem_character_iput_ (char *target, const char *source, int *tst, int *sst, int *nelems, int *pe);
+void pshmem_double_iput_ (double *target, const double *source, int *tst, int *sst, int *nelems, int *pe);
+void pshmem_integer_iput_ (int *target, const int *source, int *tst, int *sst, int *nelems, int *pe);
+void pshmem_logical_iput_ (int *target, const int *source, int *tst, int *sst, int *nelems, int *pe);
+void pshmem_real_iput_ (int *target, const int *source, int *tst, int *sst, int *nelems, int *pe);
+void pshmem_complex_iput_ (SHMEM_F_COMPLEX (float) *target, const SHMEM_F_COMPLEX (float) *source, int *tst, int *sst, int *nelems, int *pe);
+void pshmem_iput4_ (void *target, const void *source, int *tst, int *sst, int *nelems, int *pe);
+void pshmem_iput8_ (void *target, const void *source, int *tst, int *sst, int *nelems, int *pe);
+void pshmem_iput32_ (void *target, const void *source, int *tst, int *sst, int *nelems, int *pe);
+void pshmem_iput64_ (void *target, const void *source, int *tst, int *sst, int *nelems, int *pe);
+void pshmem_iput128_ (void *target, const void *source, int *tst, int *sst, int *nelems, int *pe);
+void pshmem_character_iget_ (char *target, const char *source, int *tst, int *sst, int *nelems, int *pe);
+void pshmem_double_iget_ (double *target, const double *source, int *tst, int *sst, int *nelems, int *pe);
+void pshmem_integer_iget_ (int *target, const int *source, int *tst, int *sst, int *nelems, int *pe);
+void pshmem_logical_iget_ (int *target, const int *source, int *tst, int *sst, int *nelems, int *pe);
+void pshmem_real_iget_ (int *target, const int *source, int *tst, int *sst, int *nelems, int *pe);
+void pshmem_complex_iget_ (SHMEM_F_COMPLEX (float) *target, const SHMEM_F_COMPLEX (float) *source, int *tst, int *sst, int *nelems, int *pe);
+void pshmem_iget4_ (void *target, const void *source, int *tst, int *sst, int *nelems, int *pe);
+void pshmem_iget8_ (void *target, const void *source, int *tst, int *sst, int *nelems, int *pe);
+void pshmem_iget32_ (void *target, const void *source, int *tst, int *sst, int *nelems, int *pe);
+void pshmem_iget64_ (void *target, const void *source, int *tst, int *sst, int *nelems, int *pe);
+void pshmem_iget128_ (void *target, const void *source, int *tst, int *sst, int *nelems, int *pe);
 #ifdef __cplusplus
 }
 #endif

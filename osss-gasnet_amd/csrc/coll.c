@@ -23,6 +23,10 @@
  *       form dst / sst elements apart (see alltoall_bytes for the one
  *       deliberate deviation: blocks are numbered by the index in the active
  *       set, not by the global PE number)
+ *   shmem_<T>_iput/iget, shmem_iput/iget32/64/128   src/ptp/strided.c:110-238:
+ *       target[k*tst] = source[k*sst], one element per network call there,
+ *       one strided kernel launch here (see iput_bytes / iget_bytes)
+ *   shmem_<T>_p / _g   src/ptp/putget.c: a put or get of one element
  *
  * The remote side of put/get, and every collective's source, is symmetric:
  * in the device symmetric heap (shmemx_malloc_device), which peers read over
@@ -37,7 +41,9 @@
  * HIP runtime's P2P copy contract makes the bytes visible to the peer's later
  * kernels; this library's kernels only ever write their own GPU's memory, so
  * no coherence question about a peer GPU's L2 arises); a put whose target is
- * on this GPU (a PE sharing it, or this PE) runs the copy kernel. A get into device
+ * on this GPU (a PE sharing it, or this PE) runs the copy kernel (a strided put:
+ * the strided kernel; into another GPU's memory the kernel only packs the
+ * elements and the runtime's 2-D copy places them). A get into device
  * memory, and every collective, PULLS with the streaming copy kernel: every
  * PE reads the members' sources over xGMI into its own target, between two
  * barriers -- the same producer/consumer pattern as the reduction's
@@ -584,22 +590,41 @@ void pshmem_collect64 (void *target, const void *source, size_t nelems, int PE_s
 /* ---------------------------------------------------------------------- */
 /* all-to-all                                                              */
 /* ---------------------------------------------------------------------- */
-/* d[k * dst] = s[k * sst], k < n, in host memory (elements of es = 4 or 8 bytes) */
+/* d[k * dst] = s[k * sst], k < n, in host memory (elements of es = 1, 2, 4, 8
+ * or 16 bytes; a 16-byte element moves as bytes: shmem_iput128's pointers
+ * promise no more than the caller's type does) */
 static void host_strided_copy (void *d, const void *s, size_t es, ptrdiff_t dst, ptrdiff_t sst, size_t n)
 {
     if (dst == 1 && sst == 1) {
         memmove (d, s, n * es);
-    } else if (es == 4) {
-        for (size_t k = 0; k < n; ++k)
-            ((uint32_t *) d)[(ptrdiff_t) k * dst] = ((const uint32_t *) s)[(ptrdiff_t) k * sst];
-    } else {
-        for (size_t k = 0; k < n; ++k)
-            ((uint64_t *) d)[(ptrdiff_t) k * dst] = ((const uint64_t *) s)[(ptrdiff_t) k * sst];
+        return;
     }
+#define HOST_STRIDED(Type)                                                                          \
+    for (size_t k = 0; k < n; ++k)                                                                  \
+        ((Type *) d)[(ptrdiff_t) k * dst] = ((const Type *) s)[(ptrdiff_t) k * sst];
+    switch (es) {
+    case 1:
+        HOST_STRIDED (uint8_t)
+        break;
+    case 2:
+        HOST_STRIDED (uint16_t)
+        break;
+    case 4:
+        HOST_STRIDED (uint32_t)
+        break;
+    case 8:
+        HOST_STRIDED (uint64_t)
+        break;
+    default:
+        for (size_t k = 0; k < n; ++k)
+            memcpy ((char *) d + (ptrdiff_t) k * dst * 16, (const char *) s + (ptrdiff_t) k * sst * 16, 16);
+        break;
+    }
+#undef HOST_STRIDED
 }
 
 /* k blocks of nelems elements into device memory: the copy kernel when both
- * strides are 1 (mi355_strided_pull hands those on), the strided kernel
+ * strides are 1 (mi355_strided_copy hands those on), the strided kernel
  * otherwise, 64 blocks per launch. wait as in pull_impl. */
 static void a2a_launch (const char *fn, int es, void **dsts, const void **srcs, ptrdiff_t dst, ptrdiff_t sst,
                         size_t nelems, int k, int wait)
@@ -610,7 +635,7 @@ static void a2a_launch (const char *fn, int es, void **dsts, const void **srcs, 
         if (base + g == k && wait)
             shmemi_arm_signal ();
         shmemi_timed_begin ();
-        const int rc = mi355_strided_pull (es, dsts + base, srcs + base, dst, sst, nelems, g, shmemi.stream);
+        const int rc = mi355_strided_copy (es, dsts + base, srcs + base, dst, sst, nelems, g, shmemi.stream);
         shmemi_timed_end ();
         if (rc != 0)
             shmemi_fatal ("%s: %s kernel launch failed: %d", fn, dst == 1 && sst == 1 ? "copy" : "strided", rc);
@@ -649,7 +674,7 @@ static void a2a_staged (const char *fn, int es, void **dsts, const void **srcs, 
                 pd[j] = scratch + (size_t) j * cnt * (size_t) es;
                 ps[j] = (const char *) srcs[base + j] + (ptrdiff_t) k0 * sst * es;
             }
-            const int rc = mi355_strided_pull (es, pd, ps, 1, sst, cnt, g, shmemi.stream);
+            const int rc = mi355_strided_copy (es, pd, ps, 1, sst, cnt, g, shmemi.stream);
             if (rc != 0)
                 shmemi_fatal ("%s: strided kernel launch failed: %d", fn, rc);
             SHMEMI_HIP (hipMemcpyAsync (tmp, scratch, (size_t) g * cnt * (size_t) es, hipMemcpyDeviceToHost,
@@ -700,7 +725,7 @@ static void a2a_from_host (const char *fn, int es, void **dsts, const void **src
             } else {
                 const void *sc = scratch;
                 SHMEMI_HIP (hipMemcpyAsync (scratch, tmp, cnt * (size_t) es, hipMemcpyHostToDevice, shmemi.stream));
-                const int rc = mi355_strided_pull (es, &d, &sc, dst, 1, cnt, 1, shmemi.stream);
+                const int rc = mi355_strided_copy (es, &d, &sc, dst, 1, cnt, 1, shmemi.stream);
                 if (rc != 0)
                     shmemi_fatal ("%s: strided kernel launch failed: %d", fn, rc);
             }
@@ -824,6 +849,254 @@ void pshmem_alltoalls64 (void *target, const void *source, ptrdiff_t dst, ptrdif
     (void) pSync;
     alltoall_bytes ("shmem_alltoalls64", 8, target, source, dst, sst, nelems, PE_start, logPE_stride, PE_size);
 }
+
+/* ---------------------------------------------------------------------- */
+/* strided put / get                                                       */
+/* ---------------------------------------------------------------------- */
+/* target[k * tst] = source[k * sst] for k < nelems, elements of es = 1, 2, 4,
+ * 8 or 16 bytes, one side symmetric on PE pe (device heap or host heap).
+ *
+ * Reference: src/ptp/strided.c:110-238, one shmem_<T>_p / _g network call per
+ * element in a host loop. Here a call is one launch of the strided kernel
+ * (mi355_strided_copy) wherever the GPU reaches both sides, host loops where
+ * both are host memory, and the all-to-all's single-block paths (a2a_launch,
+ * a2a_staged, a2a_from_host) in between. Both calls block like put_bytes /
+ * get_bytes: on return a get's data is in place, a put's source may be reused
+ * and its target is written. Elements between and after the strided ones are
+ * never written. */
+static void strided_entry (const char *fn, const void *target, const void *source, ptrdiff_t tst, ptrdiff_t sst,
+                           size_t nelems, int pe)
+{
+    shmemi_init_check (fn);
+    if (tst < 1 || sst < 1)
+        shmemi_fatal ("%s: strides tst %td, sst %td: both must be at least 1", fn, tst, sst);
+    if (nelems > 0 && (target == NULL || source == NULL))
+        shmemi_fatal ("%s: NULL %s (%zu elements, PE %d)", fn, target == NULL ? "target" : "source", nelems, pe);
+    if (shmemi.heap != NULL)
+        shmemi_server_stop ();
+    check_pe (fn, pe);
+}
+
+/* bytes from the first to the last element touched */
+static size_t strided_span (size_t nelems, ptrdiff_t stride, int es)
+{
+    return ((nelems - 1) * (size_t) stride + 1) * (size_t) es;
+}
+
+/* one block through the strided kernel (the copy kernel for strides 1, 1),
+ * returning when its stores have drained */
+static void strided_kernel (const char *fn, int es, void *d, const void *s, ptrdiff_t tst, ptrdiff_t sst, size_t n)
+{
+    if (d == s && tst == sst)
+        return;
+    shmemi_arm_signal ();
+    const int rc = mi355_strided_copy (es, &d, &s, tst, sst, n, 1, shmemi.stream);
+    if (rc != 0)
+        shmemi_fatal ("%s: %s kernel launch failed: %d", fn, tst == 1 && sst == 1 ? "copy" : "strided", rc);
+    shmemi_wait_signal ();
+}
+
+static void iget_bytes (const char *fn, int es, void *target, const void *source, ptrdiff_t tst, ptrdiff_t sst,
+                        size_t nelems, int pe)
+{
+    strided_entry (fn, target, source, tst, sst, nelems, pe);
+    if (nelems == 0)
+        return;
+    const size_t sspan = strided_span (nelems, sst, es);
+    const void *from = remote_addr (fn, source, sspan, pe);
+    const int from_host = shmemi_in_host_heap (source, sspan) || (pe == shmemi.mype && host_side (source));
+    void *d = target;
+    if (from_host) {
+        /* a host heap segment (mapped here) or this PE's own host memory:
+         * host loops into host memory; into device memory packed on the host
+         * and spread by the kernel */
+        a2a_from_host (fn, es, &d, &from, tst, sst, nelems, 1);
+        return;
+    }
+    need_gpu (fn);
+    shmemi_order_after_caller (0);
+    if (is_device_ptr (target)) {
+        if (target != from || tst != sst)
+            a2a_launch (fn, es, &d, &from, tst, sst, nelems, 1, 1);
+    } else if (tst == 1 && sst == 1) {
+        blocking_copy (target, from, nelems * (size_t) es);
+    } else {
+        a2a_staged (fn, es, &d, &from, tst, sst, nelems, 1);
+    }
+}
+
+/* A strided put into ANOTHER GPU's memory. This library's kernels never write
+ * another GPU's memory (the file header), so the kernel only packs: pieces of
+ * at most one scratch chunk are gathered contiguously into scratch C
+ * (dst_stride 1; a pageable source is packed on the host and copied in), and
+ * the runtime's copy places each piece on the peer-mapped pointer -- a 2-D
+ * copy of `cnt` rows of one element, tst elements apart, or a plain copy when
+ * tst is 1. SHMEM_TEST_IPUT_REMOTE_GPU=1 sends same-GPU targets here (tests). */
+static void iput_remote_gpu (const char *fn, int es, char *to, const void *source, ptrdiff_t tst, ptrdiff_t sst,
+                             size_t nelems)
+{
+    const size_t ue = (size_t) es;
+    char *scratch = shmemi.heap + shmemi.scratch_off + 2 * shmemi.scratch_chunk; /* scratch C */
+    const size_t cap = shmemi.scratch_chunk / ue;                                 /* elements per piece */
+    if (cap == 0)
+        shmemi_fatal ("%s: no device scratch to pack a put to another GPU in", fn);
+    const size_t piece = nelems < cap ? nelems : cap;
+    const char *from = is_device_ptr (source)
+                           ? (const char *) source
+                           : (const char *) shmemi_host_dev_ptr (source, strided_span (nelems, sst, es));
+    char *tmp = NULL;
+    if (from == NULL && sst != 1 && (tmp = (char *) malloc (piece * ue)) == NULL)
+        shmemi_fatal ("out of host memory");
+    for (size_t k0 = 0; k0 < nelems; k0 += piece) {
+        const size_t cnt = nelems - k0 < piece ? nelems - k0 : piece;
+        const ptrdiff_t soff = (ptrdiff_t) k0 * sst * es;
+        const void *packed = scratch;
+        if (sst == 1) {
+            packed = (const char *) source + soff; /* contiguous already */
+        } else if (from != NULL) {
+            void *pd = scratch;
+            const void *ps = from + soff;
+            const int rc = mi355_strided_copy (es, &pd, &ps, 1, sst, cnt, 1, shmemi.stream);
+            if (rc != 0)
+                shmemi_fatal ("%s: strided kernel launch failed: %d", fn, rc);
+        } else {
+            host_strided_copy (tmp, (const char *) source + soff, ue, 1, sst, cnt);
+            SHMEMI_HIP (hipMemcpyAsync (scratch, tmp, cnt * ue, hipMemcpyHostToDevice, shmemi.stream));
+        }
+        char *d = to + (ptrdiff_t) k0 * tst * es;
+        if (tst == 1)
+            SHMEMI_HIP (hipMemcpyAsync (d, packed, cnt * ue, hipMemcpyDefault, shmemi.stream));
+        else
+            SHMEMI_HIP (hipMemcpy2DAsync (d, (size_t) tst * ue, packed, ue, ue, cnt, hipMemcpyDefault, shmemi.stream));
+        SHMEMI_HIP (hipStreamSynchronize (shmemi.stream)); /* tmp and scratch are reused */
+    }
+    free (tmp);
+}
+
+static int iput_test_remote_gpu (void)
+{
+    static int v = -1;
+    if (v < 0) {
+        const char *e = getenv ("SHMEM_TEST_IPUT_REMOTE_GPU");
+        v = e != NULL && e[0] == '1';
+    }
+    return v;
+}
+
+static void iput_bytes (const char *fn, int es, void *target, const void *source, ptrdiff_t tst, ptrdiff_t sst,
+                        size_t nelems, int pe)
+{
+    strided_entry (fn, target, source, tst, sst, nelems, pe);
+    if (nelems == 0)
+        return;
+    const size_t tspan = strided_span (nelems, tst, es), sspan = strided_span (nelems, sst, es);
+    void *to = remote_addr (fn, target, tspan, pe);
+    const int to_host = shmemi_in_host_heap (target, tspan) || (pe == shmemi.mype && host_side (target));
+    if (to_host && host_side (source)) {
+        /* host memory both sides (a peer's host heap segment is mapped here):
+         * in place on return, visible to the peer after the next barrier */
+        host_strided_copy (to, source, (size_t) es, tst, sst, nelems);
+        return;
+    }
+    need_gpu (fn);
+    shmemi_order_after_caller (0);
+    if (to_host) {
+        /* device source into host memory: packed by the kernel, copied out, spread on the host */
+        if (tst == 1 && sst == 1)
+            blocking_copy (to, source, nelems * (size_t) es);
+        else
+            a2a_staged (fn, es, &to, &source, tst, sst, nelems, 1);
+        return;
+    }
+    if (!shmemi_pe_same_device (pe) || iput_test_remote_gpu ()) {
+        iput_remote_gpu (fn, es, (char *) to, source, tst, sst, nelems);
+        return;
+    }
+    /* target on this GPU (this PE's heap, or a PE sharing the GPU): the kernel
+     * writes the peer mapping; page-locked host sources go in through their
+     * device address, pageable ones are packed on the host and staged */
+    const void *from = is_device_ptr (source) ? source : shmemi_host_dev_ptr (source, sspan);
+    if (from != NULL)
+        strided_kernel (fn, es, to, from, tst, sst, nelems);
+    else
+        a2a_from_host (fn, es, &to, &source, tst, sst, nelems, 1);
+}
+
+#define STRIDED_PUTGET(Name, Type, Size)                                                            \
+    void pshmem_##Name##_iput (Type *target, const Type *source, ptrdiff_t tst, ptrdiff_t sst,      \
+                               size_t nelems, int pe)                                               \
+    {                                                                                               \
+        iput_bytes ("shmem_" #Name "_iput", Size, target, source, tst, sst, nelems, pe);           \
+    }                                                                                               \
+    void pshmem_##Name##_iget (Type *target, const Type *source, ptrdiff_t tst, ptrdiff_t sst,      \
+                               size_t nelems, int pe)                                               \
+    {                                                                                               \
+        iget_bytes ("shmem_" #Name "_iget", Size, target, source, tst, sst, nelems, pe);           \
+    }                                                                                               \
+    void shmem_##Name##_iput (Type *target, const Type *source, ptrdiff_t tst, ptrdiff_t sst,       \
+                              size_t nelems, int pe)                                                \
+        __attribute__ ((weak, alias ("pshmem_" #Name "_iput")));                                    \
+    void shmem_##Name##_iget (Type *target, const Type *source, ptrdiff_t tst, ptrdiff_t sst,       \
+                              size_t nelems, int pe)                                                \
+        __attribute__ ((weak, alias ("pshmem_" #Name "_iget")));
+
+STRIDED_PUTGET (char, char, 1)
+STRIDED_PUTGET (short, short, (int) sizeof (short))
+STRIDED_PUTGET (int, int, (int) sizeof (int))
+STRIDED_PUTGET (long, long, (int) sizeof (long))
+STRIDED_PUTGET (longlong, long long, (int) sizeof (long long))
+STRIDED_PUTGET (float, float, (int) sizeof (float))
+STRIDED_PUTGET (double, double, (int) sizeof (double))
+STRIDED_PUTGET (longdouble, long double, (int) sizeof (long double))
+
+#define SIZED_IPUTGET(Bits)                                                                         \
+    void pshmem_iput##Bits (void *target, const void *source, ptrdiff_t tst, ptrdiff_t sst,         \
+                            size_t nelems, int pe)                                                  \
+    {                                                                                               \
+        iput_bytes ("shmem_iput" #Bits, Bits / 8, target, source, tst, sst, nelems, pe);           \
+    }                                                                                               \
+    void pshmem_iget##Bits (void *target, const void *source, ptrdiff_t tst, ptrdiff_t sst,         \
+                            size_t nelems, int pe)                                                  \
+    {                                                                                               \
+        iget_bytes ("shmem_iget" #Bits, Bits / 8, target, source, tst, sst, nelems, pe);           \
+    }                                                                                               \
+    void shmem_iput##Bits (void *target, const void *source, ptrdiff_t tst, ptrdiff_t sst,          \
+                           size_t nelems, int pe)                                                   \
+        __attribute__ ((weak, alias ("pshmem_iput" #Bits)));                                        \
+    void shmem_iget##Bits (void *target, const void *source, ptrdiff_t tst, ptrdiff_t sst,          \
+                           size_t nelems, int pe)                                                   \
+        __attribute__ ((weak, alias ("pshmem_iget" #Bits)));
+
+SIZED_IPUTGET (32)
+SIZED_IPUTGET (64)
+SIZED_IPUTGET (128)
+
+/* single elements (reference src/ptp/putget.c shmem_<T>_p / _g): a put or
+ * get of one element; the strided calls above are NOT built from them */
+#define SINGLE_PG(Name, Type)                                                                       \
+    void pshmem_##Name##_p (Type *addr, Type value, int pe)                                         \
+    {                                                                                               \
+        put_bytes ("shmem_" #Name "_p", addr, &value, sizeof (Type), pe);                          \
+    }                                                                                               \
+    Type pshmem_##Name##_g (Type *addr, int pe)                                                     \
+    {                                                                                               \
+        Type value;                                                                                 \
+        memset (&value, 0, sizeof value);                                                           \
+        get_bytes ("shmem_" #Name "_g", &value, addr, sizeof (Type), pe);                          \
+        return value;                                                                               \
+    }                                                                                               \
+    void shmem_##Name##_p (Type *addr, Type value, int pe)                                          \
+        __attribute__ ((weak, alias ("pshmem_" #Name "_p")));                                       \
+    Type shmem_##Name##_g (Type *addr, int pe) __attribute__ ((weak, alias ("pshmem_" #Name "_g")));
+
+SINGLE_PG (char, char)
+SINGLE_PG (short, short)
+SINGLE_PG (int, int)
+SINGLE_PG (long, long)
+SINGLE_PG (longlong, long long)
+SINGLE_PG (float, float)
+SINGLE_PG (double, double)
+SINGLE_PG (longdouble, long double)
 
 #define WEAK(name) __attribute__ ((weak, alias ("p" #name)))
 void shmem_putmem (void *dest, const void *src, size_t nelems, int pe) WEAK (shmem_putmem);

@@ -125,3 +125,41 @@ void shmem_alltoalls32_ (void *target, const void *source, ptrdiff_t *dst, ptrdi
                          int *PE_start, int *logPE_stride, int *PE_size, int *pSync) WEAK_F (shmem_alltoalls32_);
 void shmem_alltoalls64_ (void *target, const void *source, ptrdiff_t *dst, ptrdiff_t *sst, int *nelems,
                          int *PE_start, int *logPE_stride, int *PE_size, int *pSync) WEAK_F (shmem_alltoalls64_);
+
+/* ---- strided put/get (reference src/fortran/fortran.c:482-573) ---------- */
+
+/* Fortran name -> the C entry of its element size, as the reference maps
+ * them: character 1 byte; integer, logical, real, 4 and 32: 4 bytes; double,
+ * complex, 8 and 64: 8 bytes; 128: 16 bytes. Strides and counts are INTEGERs. */
+#define F_STRIDED_ALL(X)                                                                                    \
+    X (shmem_character_iput_, pshmem_char_iput, char)                                                       \
+    X (shmem_double_iput_, pshmem_double_iput, double)                                                      \
+    X (shmem_integer_iput_, pshmem_int_iput, int)                                                           \
+    X (shmem_logical_iput_, pshmem_int_iput, int)                                                           \
+    X (shmem_real_iput_, pshmem_int_iput, int)                                                              \
+    X (shmem_complex_iput_, pshmem_iput64, float _Complex)                                                  \
+    X (shmem_iput4_, pshmem_iput32, void)                                                                   \
+    X (shmem_iput8_, pshmem_iput64, void)                                                                   \
+    X (shmem_iput32_, pshmem_iput32, void)                                                                  \
+    X (shmem_iput64_, pshmem_iput64, void)                                                                  \
+    X (shmem_iput128_, pshmem_iput128, void)                                                                \
+    X (shmem_character_iget_, pshmem_char_iget, char)                                                       \
+    X (shmem_double_iget_, pshmem_double_iget, double)                                                      \
+    X (shmem_integer_iget_, pshmem_int_iget, int)                                                           \
+    X (shmem_logical_iget_, pshmem_int_iget, int)                                                           \
+    X (shmem_real_iget_, pshmem_int_iget, int)                                                              \
+    X (shmem_complex_iget_, pshmem_iget64, float _Complex)                                                  \
+    X (shmem_iget4_, pshmem_iget32, void)                                                                   \
+    X (shmem_iget8_, pshmem_iget64, void)                                                                   \
+    X (shmem_iget32_, pshmem_iget32, void)                                                                  \
+    X (shmem_iget64_, pshmem_iget64, void)                                                                  \
+    X (shmem_iget128_, pshmem_iget128, void)
+
+#define F_STRIDED(Fname, Centry, Ctype)                                                                     \
+    void p##Fname (Ctype *target, const Ctype *source, int *tst, int *sst, int *nelems, int *pe)            \
+    {                                                                                                       \
+        Centry (target, source, (ptrdiff_t) *tst, (ptrdiff_t) *sst, (size_t) *nelems, *pe);                 \
+    }                                                                                                       \
+    void Fname (Ctype *target, const Ctype *source, int *tst, int *sst, int *nelems, int *pe) WEAK_F (Fname);
+
+F_STRIDED_ALL (F_STRIDED)

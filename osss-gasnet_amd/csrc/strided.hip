@@ -1,14 +1,16 @@
-// strided.hip -- the strided pull kernel of shmem_alltoalls32/64 (gfx950).
+// strided.hip -- the strided copy kernel of shmem_iput / shmem_iget and of
+// shmem_alltoalls32/64 (gfx950).
 //
-// The reference runs alltoalls as one shmem_iget per peer, an element-by-
-// element host loop (src/ptp/strided.c:199-206). Here one launch moves up to
-// 64 independent strided blocks (blockIdx.y = block):
+// The reference runs a strided put or get as one network call per element
+// (shmem_<T>_p / _g in a host loop, src/ptp/strided.c:110-238) and alltoalls
+// as one shmem_iget per peer (src/alltoall/alltoall-linear.c). Here one launch
+// moves up to 64 independent strided blocks (blockIdx.y = block):
 //     dst[k * dst_stride] = src[k * src_stride]        k < nelems
-// with elements of 4 or 8 bytes and strides in elements (>= 1). The sources
-// may be peers' mapped memory; every store goes to this GPU's (or this
+// with elements of 1, 2, 4, 8 or 16 bytes and strides in elements (>= 1). The
+// sources may be peers' mapped memory; every store goes to this GPU's (or this
 // process's page-locked host) memory, the rule of coll.c's file header.
 //
-// Access pattern, per side:
+// Access pattern, per side, for elements of 1 to 8 bytes:
 //   stride 1   16-byte vectors, after a head peeled so that side starts on a
 //              128-byte line (as copy_segments peels its target)
 //   stride > 1 consecutive lanes take consecutive elements, so one wave
@@ -16,12 +18,29 @@
 //              (64 * stride * size bytes); 1 / stride of every fetched line
 //              is useful, up to one element per line
 // One side contiguous and the other strided cannot have both from registers
-// alone (a lane's 16-byte vector holds V = 4 or 2 CONSECUTIVE elements, the
-// lane-consecutive accesses hold elements 256 apart), so a block turns its
+// alone (a lane's 16-byte vector holds V = 16, 8, 4 or 2 CONSECUTIVE elements,
+// the lane-consecutive accesses hold elements 256 apart), so a block turns its
 // tile of 256 * V elements through 4 KiB of LDS: written one way, read the
 // other, between two block barriers. The loads of the next tile are issued
 // before the stores of this one. Both sides contiguous is the copy kernel
 // (mi355_copy_segments); both strided needs no LDS.
+//
+// The tile is addressed in ELEMENTS on the lane-consecutive side (element
+// j * 256 + tid, a byte, short, dword or qword access) and in 16-byte vectors
+// on the other (vector tid = elements tid * V ... tid * V + V - 1), so the two
+// views agree for every sizeof(T) dividing 16. With 1- and 2-byte elements the
+// element-side LDS accesses are sub-dword: the 4 (2) lanes whose elements
+// share a dword hit one bank, 32 lanes cover 8 (16) banks. That is within
+// what ds_write_b32's issue already costs (MI355X: a 4-way store conflict
+// doubles a 4-cycle instruction). Measured (strided
+// put/get): the forms that store with a stride take the same time from 8-byte
+// elements down to 1-byte ones, bound by partially written lines; the 1-byte
+// gathers are 40-45 % behind the 4-byte ones, bound by their V = 16 one-byte
+// global loads per lane and tile, which packing in registers would not remove.
+//
+// A 16-byte element is a vector already: no LDS and no tile, every lane moves
+// one element per slot on both sides (the "both" form with T = u32x4),
+// whatever the strides.
 //
 // Every offset is 64-bit: nelems * stride * size passes 4 GiB easily.
 // Grid-stride over a capped grid; the tile loop's trip count is uniform per
@@ -162,7 +181,7 @@ __global__ __launch_bounds__(kBlock) void strided_pull(StridedParams<NS> p) {
 
 template <typename T, int MODE>
 static int strided_launch(const StridedParams<kStridedMaxSeg> &p, int used, hipStream_t st) {
-    constexpr int V = 16 / sizeof(T);
+    constexpr int V = 16 / sizeof(T);  // 1 for a 16-byte element (no tile: STRIDED_BOTH only)
     // a few resident blocks per CU: the strided side is latency-bound (one
     // element per lane per load), more waves keep more lines in flight
     constexpr int kPerCU = 8;
@@ -192,10 +211,10 @@ static int strided_mode(const StridedParams<kStridedMaxSeg> &p, int used, hipStr
 
 using namespace mi355k;
 
-static int strided_pull_impl(int elem_size, void *const *dsts, const void *const *srcs, ptrdiff_t dst_stride,
+static int strided_copy_impl(int elem_size, void *const *dsts, const void *const *srcs, ptrdiff_t dst_stride,
                              ptrdiff_t src_stride, size_t nelems, int nseg, void *stream) {
-    if ((elem_size != 4 && elem_size != 8) || dst_stride < 1 || src_stride < 1 || nseg < 0 ||
-        nseg > kStridedMaxSeg)
+    if ((elem_size != 1 && elem_size != 2 && elem_size != 4 && elem_size != 8 && elem_size != 16) || dst_stride < 1 ||
+        src_stride < 1 || nseg < 0 || nseg > kStridedMaxSeg)
         return MI355_E_INVAL;
     if (nseg > 0 && (dsts == nullptr || srcs == nullptr)) return MI355_E_INVAL;
     if (dst_stride == 1 && src_stride == 1) {
@@ -221,17 +240,34 @@ static int strided_pull_impl(int elem_size, void *const *dsts, const void *const
     p.dst_stride = dst_stride;
     p.src_stride = src_stride;
     p.n = nelems;
-    return elem_size == 4 ? strided_mode<uint32_t>(p, used, (hipStream_t)stream)
-                          : strided_mode<uint64_t>(p, used, (hipStream_t)stream);
+    hipStream_t st = (hipStream_t)stream;
+    switch (elem_size) {
+        case 1: return strided_mode<uint8_t>(p, used, st);
+        case 2: return strided_mode<uint16_t>(p, used, st);
+        case 4: return strided_mode<uint32_t>(p, used, st);
+        case 8: return strided_mode<uint64_t>(p, used, st);
+        default: return strided_launch<u32x4, STRIDED_BOTH>(p, used, st);  // an element is a vector
+    }
 }
 
 // Every error return cancels an armed signal/timing request, as in combine.hip.
-extern "C" int mi355_strided_pull(int elem_size, void *const *dsts, const void *const *srcs, ptrdiff_t dst_stride,
-                                  ptrdiff_t src_stride, size_t nelems, int nseg, void *stream) {
-    const int rc = strided_pull_impl(elem_size, dsts, srcs, dst_stride, src_stride, nelems, nseg, stream);
+static int strided_cancel_on_error(int rc) {
     if (rc != 0) {
         t_sig = Signal{nullptr, nullptr, 0};
         t_ev_start = t_ev_stop = nullptr;
     }
     return rc;
+}
+
+extern "C" int mi355_strided_copy(int elem_size, void *const *dsts, const void *const *srcs, ptrdiff_t dst_stride,
+                                  ptrdiff_t src_stride, size_t nelems, int nseg, void *stream) {
+    return strided_cancel_on_error(
+        strided_copy_impl(elem_size, dsts, srcs, dst_stride, src_stride, nelems, nseg, stream));
+}
+
+// The all-to-all's front: 4- and 8-byte elements only, the same launches.
+extern "C" int mi355_strided_pull(int elem_size, void *const *dsts, const void *const *srcs, ptrdiff_t dst_stride,
+                                  ptrdiff_t src_stride, size_t nelems, int nseg, void *stream) {
+    if (elem_size != 4 && elem_size != 8) return strided_cancel_on_error(MI355_E_INVAL);
+    return mi355_strided_copy(elem_size, dsts, srcs, dst_stride, src_stride, nelems, nseg, stream);
 }

@@ -146,6 +146,7 @@ void shmemi_trace_show_info (void)
                                "staging them through scratch"},
         {"SHMEM_EXTERNAL_MAP_CACHE", "peers' mapped allocations kept open (default 64, least recently used closed)"},
         {"SHMEM_PEER_ACQUIRE", "1/0: system-scope L2 acquire before reading peers' buffers (default: on if a peer is on another GPU)"},
+        {"SHMEM_TEST_IPUT_REMOTE_GPU", "1: strided puts to PEs on this GPU take the path of a target on another GPU (tests)"},
     };
     shmemi_trace_emit (SHMEMI_LOG_INFO, "environment variables understood by this build:");
     for (size_t i = 0; i < sizeof vars / sizeof vars[0]; ++i)

@@ -311,6 +311,45 @@ class Shmem:
         s = (_vp * len(srcs))(*srcs)
         return f(elem_size, d, s, dst_stride, src_stride, nelems, len(dsts), stream)
 
+    def strided_copy(self, elem_size, dsts, srcs, dst_stride, src_stride, nelems, stream=None):
+        """mi355_strided_copy: the same for elements of 1, 2, 4, 8 or 16 bytes"""
+        f = self._fns.get("mi355_strided_copy")
+        if f is None:
+            f = self.lib.mi355_strided_copy
+            f.restype = _i
+            f.argtypes = [_i, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _pd, _pd, _sz, _i, _vp]
+            self._fns["mi355_strided_copy"] = f
+        d = (_vp * len(dsts))(*dsts)
+        s = (_vp * len(srcs))(*srcs)
+        return f(elem_size, d, s, dst_stride, src_stride, nelems, len(dsts), stream)
+
+    # ---- strided put/get (include/shmem.h)
+    _STRIDED_NAMES = {1: "shmem_char_i{}", 2: "shmem_short_i{}", 4: "shmem_i{}32", 8: "shmem_i{}64",
+                      16: "shmem_i{}128"}
+
+    def _strided_fn(self, op, elem_size):
+        if elem_size not in self._STRIDED_NAMES:
+            raise ValueError("elem_size must be 1, 2, 4, 8 or 16")
+        name = self._STRIDED_NAMES[elem_size].format(op)
+        f = self._fns.get(name)
+        if f is None:
+            f = getattr(self.lib, name)
+            f.restype = None
+            f.argtypes = [_vp, _vp, _pd, _pd, _sz, _i]
+            self._fns[name] = f
+        return f
+
+    def iput(self, elem_size, target, source, tst, sst, nelems, pe):
+        """shmem_iput: target_on_pe[k * tst] = source[k * sst] for k < nelems
+        (shmem_char_iput, shmem_short_iput, shmem_iput32/64/128 by elem_size);
+        target symmetric, strides in elements. Blocking."""
+        self._strided_fn("put", elem_size)(target, source, tst, sst, nelems, pe)
+
+    def iget(self, elem_size, target, source, tst, sst, nelems, pe):
+        """shmem_iget: target[k * tst] = source_on_pe[k * sst] for k < nelems;
+        source symmetric. Blocking."""
+        self._strided_fn("get", elem_size)(target, source, tst, sst, nelems, pe)
+
     def heap_tensor(self, n, dtype):
         """A 1-D torch tensor of n elements of torch dtype `dtype` in the
         device symmetric heap (collective, like shmemx_malloc_device): the
