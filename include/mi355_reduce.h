@@ -47,7 +47,10 @@ enum mi355_dtype {
     MI355_LONGDOUBLE = 6, /* x87 80-bit extended in a 16-byte slot        */
     MI355_COMPLEXF = 7,   /* {float re, im}                               */
     MI355_COMPLEXD = 8,   /* {double re, im}                              */
-    MI355_NUM_DTYPES = 9
+    /* not in the reference (shmemx.h, shmemx_half_* / shmemx_bfloat16_*):    */
+    MI355_HALF = 9,       /* IEEE binary16, as its 16 bits                */
+    MI355_BFLOAT16 = 10,  /* the upper 16 bits of binary32                */
+    MI355_NUM_DTYPES = 11
 };
 
 #define MI355_E_INVAL  (-1)   /* bad op/dtype/pointer/count        */
@@ -56,7 +59,11 @@ enum mi355_dtype {
 /* Bytes per element of a dtype (0 for an unknown dtype). */
 size_t mi355_dtype_size (int dtype);
 
-/* 1 if (op, dtype) is one of the 44 reference reductions. */
+/* 1 if (op, dtype) is a reduction this layer has: the 44 of the reference,
+ * and sum, prod, min and max of the two 16-bit float types (each step of
+ * their folds rounded to the type, to nearest even; a NaN out of sum or prod
+ * is the canonical quiet NaN 0x7E00 / 0x7FC0; min and max return the chosen
+ * operand's bits). */
 int mi355_op_supported (int op, int dtype);
 
 /* dst[i] = (((srcs[0][i] op srcs[1][i]) op srcs[2][i]) ... op srcs[nsrc-1][i])

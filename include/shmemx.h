@@ -388,6 +388,71 @@ void shmemx_longdouble_min_to_all_on_stream (long double *target, long double *s
         int nreduce, int PE_start, int logPE_stride, int PE_size,
         long double *pWrk, long *pSync, void *stream);
 
+/* ---- 16-bit floating-point reductions (not in the reference) ----
+ * Elements are passed as their 16 bits: half is IEEE binary16, bfloat16 the
+ * upper 16 bits of binary32. sum, prod, min and max; no bitwise operators.
+ * The fold order is float's: in SHMEMX_ORDER_REFERENCE PE q receives
+ * (((src_q op src_m0) op src_m1) ...) over the other members m0 < m1 < ... of
+ * the active set, in SHMEMX_ORDER_PE_START every PE receives PE_start's
+ * result. EVERY step is rounded to the type: for sum and prod
+ * r = round (float (a) op float (b)), to nearest, ties to even, subnormals
+ * kept, overflow to +-inf -- the correctly rounded 16-bit operation -- and a
+ * NaN result is the canonical quiet NaN (0x7E00 half, 0x7FC0 bfloat16)
+ * whatever the operands' payloads. min and max are `a < b ? a : b` and
+ * `a > b ? a : b` on the values and return the chosen operand's bits
+ * unchanged (a NaN or a +-0 pair selects by position, as for float). The
+ * result does not depend on the schedule. There is no pshmem_ twin.
+ * These types take the multi-launch schedules (no one-launch fused kernel or
+ * persistent server yet), and SHMEM_REDUCE_ALGORITHM=rccl falls back to P2P. */
+typedef unsigned short shmemx_half_t, shmemx_bfloat16_t;
+void shmemx_half_sum_to_all (shmemx_half_t *target, shmemx_half_t *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        shmemx_half_t *pWrk, long *pSync);
+void shmemx_half_prod_to_all (shmemx_half_t *target, shmemx_half_t *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        shmemx_half_t *pWrk, long *pSync);
+void shmemx_half_max_to_all (shmemx_half_t *target, shmemx_half_t *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        shmemx_half_t *pWrk, long *pSync);
+void shmemx_half_min_to_all (shmemx_half_t *target, shmemx_half_t *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        shmemx_half_t *pWrk, long *pSync);
+void shmemx_bfloat16_sum_to_all (shmemx_bfloat16_t *target, shmemx_bfloat16_t *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        shmemx_bfloat16_t *pWrk, long *pSync);
+void shmemx_bfloat16_prod_to_all (shmemx_bfloat16_t *target, shmemx_bfloat16_t *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        shmemx_bfloat16_t *pWrk, long *pSync);
+void shmemx_bfloat16_max_to_all (shmemx_bfloat16_t *target, shmemx_bfloat16_t *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        shmemx_bfloat16_t *pWrk, long *pSync);
+void shmemx_bfloat16_min_to_all (shmemx_bfloat16_t *target, shmemx_bfloat16_t *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        shmemx_bfloat16_t *pWrk, long *pSync);
+void shmemx_half_sum_to_all_on_stream (shmemx_half_t *target, shmemx_half_t *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        shmemx_half_t *pWrk, long *pSync, void *stream);
+void shmemx_half_prod_to_all_on_stream (shmemx_half_t *target, shmemx_half_t *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        shmemx_half_t *pWrk, long *pSync, void *stream);
+void shmemx_half_max_to_all_on_stream (shmemx_half_t *target, shmemx_half_t *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        shmemx_half_t *pWrk, long *pSync, void *stream);
+void shmemx_half_min_to_all_on_stream (shmemx_half_t *target, shmemx_half_t *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        shmemx_half_t *pWrk, long *pSync, void *stream);
+void shmemx_bfloat16_sum_to_all_on_stream (shmemx_bfloat16_t *target, shmemx_bfloat16_t *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        shmemx_bfloat16_t *pWrk, long *pSync, void *stream);
+void shmemx_bfloat16_prod_to_all_on_stream (shmemx_bfloat16_t *target, shmemx_bfloat16_t *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        shmemx_bfloat16_t *pWrk, long *pSync, void *stream);
+void shmemx_bfloat16_max_to_all_on_stream (shmemx_bfloat16_t *target, shmemx_bfloat16_t *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        shmemx_bfloat16_t *pWrk, long *pSync, void *stream);
+void shmemx_bfloat16_min_to_all_on_stream (shmemx_bfloat16_t *target, shmemx_bfloat16_t *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        shmemx_bfloat16_t *pWrk, long *pSync, void *stream);
 
 #ifdef __cplusplus
 }

@@ -325,6 +325,8 @@ extern "C" size_t mi355_dtype_size(int dtype) {
     case MI355_LONGDOUBLE: return 16;
     case MI355_COMPLEXF: return 8;
     case MI355_COMPLEXD: return 16;
+    case MI355_HALF:
+    case MI355_BFLOAT16: return 2;
     default: return 0;
     }
 }
@@ -411,6 +413,8 @@ static int combine_impl(int op, int dtype, void *dst, const void *const *srcs, i
     case MI355_LONGDOUBLE: return combine_longdouble(op, dst, srcs, nsrc, n, st);
     case MI355_COMPLEXF: return combine_complexf(op, dst, srcs, nsrc, n, st);
     case MI355_COMPLEXD: return combine_complexd(op, dst, srcs, nsrc, n, st);
+    case MI355_HALF: return combine_half(op, dst, srcs, nsrc, n, st);
+    case MI355_BFLOAT16: return combine_bfloat16(op, dst, srcs, nsrc, n, st);
     default: return MI355_E_INVAL;
     }
 }
@@ -445,6 +449,8 @@ static int combine_orders_impl(int op, int dtype, void *const *dsts, const void 
     case MI355_LONGDOUBLE: return orders_longdouble(op, dsts, srcs, nsrc, n, st);
     case MI355_COMPLEXF: return orders_complexf(op, dsts, srcs, nsrc, n, st);
     case MI355_COMPLEXD: return orders_complexd(op, dsts, srcs, nsrc, n, st);
+    case MI355_HALF: return orders_half(op, dsts, srcs, nsrc, n, st);
+    case MI355_BFLOAT16: return orders_bfloat16(op, dsts, srcs, nsrc, n, st);
     default: return MI355_E_INVAL;
     }
 }

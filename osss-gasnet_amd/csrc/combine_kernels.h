@@ -163,6 +163,10 @@ __device__ __forceinline__ void fold_vectors(const CombineParams &p) {
 #pragma unroll
                     for (int e = 0; e < V; ++e) acc.e[e] = apply_fast<OP>(acc.e[e], x[u][k].e[e]);
                 }
+                if constexpr (NSRC > 1 && f16_chain<OP, T>()) {
+#pragma unroll
+                    for (int e = 0; e < V; ++e) acc.e[e] = chain_end<OP>(acc.e[e]);
+                }
                 if constexpr (has_fast_form<OP, T>()) {
                     // a NaN came out somewhere: the reference's operator, step by step
                     bool redo = false;
@@ -465,6 +469,10 @@ __device__ __forceinline__ void orders_one(const OrdersParams &p, const Pack<T> 
             if (k == q) continue;
 #pragma unroll
             for (int e = 0; e < V; ++e) acc.e[e] = apply_fast<OP>(acc.e[e], x[k].e[e]);
+        }
+        if constexpr (NSRC > 1 && f16_chain<OP, T>()) {
+#pragma unroll
+            for (int e = 0; e < V; ++e) acc.e[e] = chain_end<OP>(acc.e[e]);
         }
 #pragma unroll
         for (int e = 0; e < V; ++e) redo |= redo_needed<OP>(acc.e[e]);
@@ -1031,6 +1039,8 @@ MI355_COMBINE_DECL(double)
 MI355_COMBINE_DECL(longdouble)
 MI355_COMBINE_DECL(complexf)
 MI355_COMBINE_DECL(complexd)
+MI355_COMBINE_DECL(half)
+MI355_COMBINE_DECL(bfloat16)
 #undef MI355_COMBINE_DECL
 
 }  // namespace mi355k

@@ -15,6 +15,10 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 struct cplxf { float re, im; };
 struct cplxd { double re, im; };
+// 16-bit floats as bit patterns (shmemx_half_t, shmemx_bfloat16_t): IEEE
+// binary16, and the upper half of binary32
+struct f16 { uint16_t bits; };
+struct bf16 { uint16_t bits; };
 
 // ---------------------------------------------------------------------------
 // element operators (reduce-op.c:79-158)
@@ -72,6 +76,71 @@ __device__ __forceinline__ T fp_op(T a, T b) {
     else if constexpr (OP == MI355_OP_PROD) return x86_result(a * b, a, b);
     else if constexpr (OP == MI355_OP_MIN) return a < b ? a : b;
     else return a > b ? a : b;
+}
+
+// 16-bit floats (not in the reference; DESIGN section 2, "16-bit floats").
+// Every step of a fold is rounded to the type: r = round(float(a) op float(b)),
+// the widening exact, the operation in binary32, the rounding to nearest even
+// with subnormals kept (the kernels run with both denormal modes on, hipcc's
+// default). For both types binary32's 24 bits are at least 2p + 2, so this is
+// the correctly rounded 16-bit operation. Half is written as that native
+// operation (v_add_f16 / v_mul_f16 and their packed forms): written as
+// (_Float16)(float * float) the compiler selects v_fma_mixlo_f16 a, b, +0,
+// whose +0 addend turns a product of -0 into +0. For bfloat16 the operation
+// is binary32's and the rounding v_cvt_pk_bf16_f32. A NaN result is the canonical quiet NaN whatever the
+// operands' payloads were (the hardware's own propagation picks operands by
+// rules of its own), so a + b and b + a have the same bits. min/max compare
+// the values and return the chosen operand's 16 bits unchanged: the select is
+// on the bit patterns, which keeps v_min/v_max (number-preferring, quieting)
+// out of it.
+template <typename T> struct F16Traits;
+template <> struct F16Traits<f16> {
+    static constexpr uint16_t canonical_nan = 0x7E00, inf = 0x7C00;
+    static __device__ __forceinline__ float widen(f16 a) { return (float)__builtin_bit_cast(_Float16, a.bits); }
+    // a + b or a * b rounded to the type; nan: the result is a NaN
+    template <bool SUM>
+    static __device__ __forceinline__ uint16_t arith(f16 a, f16 b, bool &nan) {
+        const _Float16 x = __builtin_bit_cast(_Float16, a.bits), y = __builtin_bit_cast(_Float16, b.bits);
+        const _Float16 r = SUM ? x + y : x * y;
+        nan = r != r;
+        return __builtin_bit_cast(uint16_t, r);
+    }
+};
+template <> struct F16Traits<bf16> {
+    static constexpr uint16_t canonical_nan = 0x7FC0, inf = 0x7F80;
+    static __device__ __forceinline__ float widen(bf16 a) { return __builtin_bit_cast(float, (uint32_t)a.bits << 16); }
+    template <bool SUM>
+    static __device__ __forceinline__ uint16_t arith(bf16 a, bf16 b, bool &nan) {
+        const float x = widen(a), y = widen(b);
+        const float r = SUM ? x + y : x * y;
+        nan = __builtin_isnan(r);
+        return __builtin_bit_cast(uint16_t, (__bf16)r);
+    }
+};
+
+template <typename T>
+constexpr bool is_f16_type() {
+    return std::is_same<T, f16>::value || std::is_same<T, bf16>::value;
+}
+
+// CANON = false: the step inside a chain of sums or products whose END is
+// canonicalised (chain_end): a NaN stays a NaN through every later step
+// and through both roundings (the operation's NaN is quiet, and the
+// conversions keep a quiet NaN a NaN), so which NaN travels does not matter.
+// Two VALU operations fewer per element and step.
+template <int OP, typename T, bool CANON = true>
+__device__ __forceinline__ T f16_op(T a, T b) {
+    using F = F16Traits<T>;
+    if constexpr (OP == MI355_OP_SUM || OP == MI355_OP_PROD) {
+        bool nan;
+        const uint16_t r = F::template arith<OP == MI355_OP_SUM>(a, b, nan);
+        if constexpr (!CANON) return T{r};
+        return T{nan ? F::canonical_nan : r};
+    } else {
+        const float x = F::widen(a), y = F::widen(b);
+        if constexpr (OP == MI355_OP_MIN) return T{x < y ? a.bits : b.bits};
+        return T{x > y ? a.bits : b.bits};
+    }
 }
 
 // libgcc __muldc3/__mulsc3 (C99 Annex G.5.1) as compiled in this image (GCC
@@ -146,6 +215,8 @@ __device__ __forceinline__ T apply(T a, T b) {
         return cplx_op<OP>(a, b);
     else if constexpr (std::is_same<T, x80>::value)
         return x80_op<OP>(a, b);
+    else if constexpr (std::is_same<T, f16>::value || std::is_same<T, bf16>::value)
+        return f16_op<OP>(a, b);
     else if constexpr (std::is_floating_point<T>::value)
         return fp_op<OP>(a, b);
     else
@@ -167,9 +238,30 @@ constexpr bool has_fast_form() {
     return fp && (OP == MI355_OP_SUM || OP == MI355_OP_PROD);
 }
 
+// 16-bit float sums and products: the steps of a vector loop's chain leave
+// the NaN as it comes (f16_op CANON = false); chain_end() makes it the
+// canonical one. No redo: has_fast_form() stays false for them.
+template <int OP, typename T>
+constexpr bool f16_chain() {
+    return is_f16_type<T>() && (OP == MI355_OP_SUM || OP == MI355_OP_PROD);
+}
+
+// The end of a chain of apply_fast() steps (at least one step).
+template <int OP, typename T>
+__device__ __forceinline__ T chain_end(T r) {
+    if constexpr (f16_chain<OP, T>()) {
+        using F = F16Traits<T>;
+        return T{(uint16_t)((r.bits & 0x7FFF) > F::inf ? F::canonical_nan : r.bits)};
+    } else {
+        return r;
+    }
+}
+
 template <int OP, typename T>
 __device__ __forceinline__ T apply_fast(T a, T b) {
-    if constexpr (!has_fast_form<OP, T>()) {
+    if constexpr (f16_chain<OP, T>()) {
+        return f16_op<OP, T, false>(a, b);
+    } else if constexpr (!has_fast_form<OP, T>()) {
         return apply<OP>(a, b);
     } else if constexpr (std::is_floating_point<T>::value) {
         return OP == MI355_OP_SUM ? a + b : a * b;
@@ -193,11 +285,13 @@ __device__ __forceinline__ bool redo_needed(const T &r) {
     else return __builtin_isnan(r.re) | __builtin_isnan(r.im);
 }
 
-// Which (op, type) pairs exist: reduce-op.c:405-448.
+// Which (op, type) pairs exist: reduce-op.c:405-448, and sum/prod/min/max
+// of the 16-bit floats.
 template <int OP, typename T>
 constexpr bool valid_pair() {
     constexpr bool is_int = std::is_integral<T>::value;
-    constexpr bool is_real = std::is_floating_point<T>::value || std::is_same<T, x80>::value;
+    constexpr bool is_real = std::is_floating_point<T>::value || std::is_same<T, x80>::value ||
+                             std::is_same<T, f16>::value || std::is_same<T, bf16>::value;
     constexpr bool is_cplx = std::is_same<T, cplxf>::value || std::is_same<T, cplxd>::value;
     if (OP == MI355_OP_SUM || OP == MI355_OP_PROD) return is_int || is_real || is_cplx;
     if (OP == MI355_OP_AND || OP == MI355_OP_OR || OP == MI355_OP_XOR) return is_int;

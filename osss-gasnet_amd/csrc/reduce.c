@@ -180,15 +180,25 @@ void mi355_shard_bounds (size_t n, size_t es, int size, int i, size_t *lo, size_
  * where both operands are NaNs SSE returns the FIRST one (ops.h x86_result),
  * so the two members' results differ in payload. x87 long double returns the
  * NaN with the larger significand whatever the order (x80.h), so its
- * two-member sum/prod agree. */
+ * two-member sum/prod agree. So do half's and bfloat16's (shmemx.h): a NaN
+ * out of their sum or prod is the canonical one whatever the operands were. */
 static int order_sensitive (int op, int dtype, int size)
 {
     if (shmemi.order != SHMEMX_ORDER_REFERENCE || size < 2)
         return 0;
     if (dtype != MI355_FLOAT && dtype != MI355_DOUBLE && dtype != MI355_LONGDOUBLE && dtype != MI355_COMPLEXF &&
-        dtype != MI355_COMPLEXD)
+        dtype != MI355_COMPLEXD && dtype != MI355_HALF && dtype != MI355_BFLOAT16)
         return 0;
-    return size > 2 || op == MI355_OP_MIN || op == MI355_OP_MAX || dtype != MI355_LONGDOUBLE;
+    return size > 2 || op == MI355_OP_MIN || op == MI355_OP_MAX ||
+           (dtype != MI355_LONGDOUBLE && dtype != MI355_HALF && dtype != MI355_BFLOAT16);
+}
+
+/* The one-launch fused kernel and the persistent server (fused.hip) have no
+ * instantiations for the 16-bit float types: their calls take the
+ * multi-launch schedules at every size. */
+static int fused_dtype (int dtype)
+{
+    return dtype != MI355_HALF && dtype != MI355_BFLOAT16;
 }
 
 /* The shard schedules deliver every member's order up to
@@ -584,7 +594,7 @@ static void p2p_any (int op, int dtype, size_t es, size_t dst_off, size_t src_of
 static int fused_eligible (int op, int dtype, size_t es, size_t dst_off, size_t src_off, size_t n,
                            const struct aset *s)
 {
-    return s->size > 1 && s->size <= MI355_FUSED_MAX_MEMBERS && n * es <= shmemi.fused_max &&
+    return fused_dtype (dtype) && s->size > 1 && s->size <= MI355_FUSED_MAX_MEMBERS && n * es <= shmemi.fused_max &&
            shmemi.npes <= MI355_SIG_RSDONE &&
            shmemi.sigmem != NULL && ((dst_off | src_off) & 15) == 0 && es <= 256 &&
            (dst_off == src_off || !ranges_overlap (dst_off, src_off, n * es)) &&
@@ -925,7 +935,8 @@ static void reduce_symmetric (int op, int dtype, size_t es, size_t dst_off, size
             return;
         }
         if (!overlap) {
-            if (shmemi.srv.enabled && nbytes <= shmemi.fused_max && ((dst_off | src_off) & 15) == 0) {
+            if (shmemi.srv.enabled && fused_dtype (dtype) && nbytes <= shmemi.fused_max &&
+                ((dst_off | src_off) & 15) == 0) {
                 fused_range (op, dtype, es, dst_off, src_off, n, s, NULL, NULL); /* persistent server */
                 return;
             }
@@ -1481,7 +1492,7 @@ static void reduce_on_stream (int op, int dtype, const char *fn, void *target, c
         if (order_sensitive (op, dtype, s.size) && !ordered)
             shmemi_fatal ("%s: %d PEs: the stream-ordered schedules deliver each PE's reference order up to %d "
                           "PEs (set SHMEM_REDUCE_ORDER=pe_start)", fn, s.size, MI355_ORDERS_MAX_SOURCES);
-        if (n * es <= shmemi.fused_max && ((dst_off | src_off) & 15) == 0 && es <= 256 &&
+        if (fused_dtype (dtype) && n * es <= shmemi.fused_max && ((dst_off | src_off) & 15) == 0 && es <= 256 &&
             (!ordered || (size_t) (s.size - 1) * shard_chunk (n, es, s.size) * es <= shmemi.order_chunk)) {
             a.op = op;
             a.dtype = dtype;
@@ -1594,3 +1605,34 @@ MINMAX (longlong, long long, MI355_LONGLONG)
 MINMAX (double, double, MI355_DOUBLE)
 MINMAX (float, float, MI355_FLOAT)
 MINMAX (longdouble, long double, MI355_LONGDOUBLE)
+
+/* ---------------------------------------------------------------------- */
+/* 16-bit floats (shmemx.h): not in the reference, so shmemx_ names only   */
+/* ---------------------------------------------------------------------- */
+#define SHMEMX_REDUCE(Name, Op, DT, OPC)                                                             \
+    void shmemx_##Name##_##Op##_to_all (shmemx_##Name##_t *target, shmemx_##Name##_t *source,        \
+                                        int nreduce, int PE_start, int logPE_stride, int PE_size,    \
+                                        shmemx_##Name##_t *pWrk, long *pSync)                        \
+    {                                                                                                \
+        (void) pWrk;                                                                                 \
+        reduce_impl (OPC, DT, "shmemx_" #Name "_" #Op "_to_all", target, source, nreduce, PE_start, \
+                     logPE_stride, PE_size, pSync);                                                  \
+    }                                                                                                \
+    void shmemx_##Name##_##Op##_to_all_on_stream (shmemx_##Name##_t *target,                         \
+                                                  shmemx_##Name##_t *source, int nreduce,            \
+                                                  int PE_start, int logPE_stride, int PE_size,       \
+                                                  shmemx_##Name##_t *pWrk, long *pSync, void *stream) \
+    {                                                                                                \
+        (void) pWrk;                                                                                 \
+        (void) pSync;                                                                                \
+        reduce_on_stream (OPC, DT, "shmemx_" #Name "_" #Op "_to_all_on_stream", target, source,     \
+                          nreduce, PE_start, logPE_stride, PE_size, stream);                         \
+    }
+#define SHMEMX_REDUCE_TYPE(Name, DT)                 \
+    SHMEMX_REDUCE (Name, sum, DT, MI355_OP_SUM)      \
+    SHMEMX_REDUCE (Name, prod, DT, MI355_OP_PROD)    \
+    SHMEMX_REDUCE (Name, max, DT, MI355_OP_MAX)      \
+    SHMEMX_REDUCE (Name, min, DT, MI355_OP_MIN)
+
+SHMEMX_REDUCE_TYPE (half, MI355_HALF)
+SHMEMX_REDUCE_TYPE (bfloat16, MI355_BFLOAT16)

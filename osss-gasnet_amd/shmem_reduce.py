@@ -19,15 +19,18 @@ LIB_PATH = os.path.join(LIB_DIR, "libshmem_reduce.so")
 
 OPS = ["sum", "prod", "and", "or", "xor", "min", "max"]           # enum mi355_op
 DTYPES = ["short", "int", "long", "longlong", "float", "double",   # enum mi355_dtype
-          "longdouble", "complexf", "complexd"]
+          "longdouble", "complexf", "complexd", "half", "bfloat16"]
 NP = {
     "short": np.int16, "int": np.int32, "long": np.int64, "longlong": np.int64,
     "float": np.float32, "double": np.float64, "longdouble": np.longdouble,
     "complexf": np.complex64, "complexd": np.complex128,
+    "half": np.float16, "bfloat16": np.uint16,   # numpy has no bfloat16: its bit patterns
 }
+# the 16-bit float types are not in the reference: their entry points are shmemx_<T>_<op>_to_all
+SHMEMX_DTYPES = ("half", "bfloat16")
 # torch dtype name -> the shmem type whose C type has its layout (LP64: long = long long = int64)
 TORCH_DTYPES = {"int16": "short", "int32": "int", "int64": "long", "float32": "float", "float64": "double",
-                "complex64": "complexf", "complex128": "complexd"}
+                "complex64": "complexf", "complex128": "complexd", "float16": "half", "bfloat16": "bfloat16"}
 ALGORITHMS = {"auto": 0, "p2p": 1, "exact": 2, "rccl": 3}          # enum shmemx_reduce_algorithm
 ORDERS = {"reference": 0, "pe_start": 1}                            # enum shmemx_reduce_order
 SHMEM_REDUCE_SYNC_SIZE = 128
@@ -38,6 +41,22 @@ _vp = ctypes.c_void_p
 _sz = ctypes.c_size_t
 _i = ctypes.c_int
 _pd = ctypes.c_ssize_t  # ptrdiff_t
+
+
+def bf16_from_f32(array):
+    """float32 values -> bfloat16 bit patterns (uint16): round to nearest,
+    ties to even, subnormals kept, overflow to +-inf; a NaN becomes the
+    canonical quiet NaN 0x7FC0 (the library's sum/prod step, shmemx.h)."""
+    a = np.ascontiguousarray(array, dtype=np.float32)
+    u = a.view(np.uint32).astype(np.uint64)
+    bits = ((u + 0x7FFF + ((u >> 16) & 1)) >> 16).astype(np.uint16)
+    return np.where(np.isnan(a), np.uint16(0x7FC0), bits)
+
+
+def bf16_to_f32(bits):
+    """bfloat16 bit patterns (uint16) -> the float32 values they denote (exact)"""
+    b = np.ascontiguousarray(bits, dtype=np.uint16)
+    return (b.astype(np.uint32) << 16).view(np.float32)
 
 
 class CallInfo(ctypes.Structure):
@@ -110,7 +129,8 @@ class Shmem:
     def _reduction(self, op, dtype):
         f = self._fns.get((op, dtype))
         if f is None:
-            f = getattr(self.lib, f"shmem_{dtype}_{op}_to_all")
+            prefix = "shmemx" if dtype in SHMEMX_DTYPES else "shmem"
+            f = getattr(self.lib, f"{prefix}_{dtype}_{op}_to_all")
             f.restype = None
             f.argtypes = [_vp, _vp, _i, _i, _i, _i, _vp, _vp]
             self._fns[(op, dtype)] = f
@@ -231,7 +251,9 @@ class Shmem:
 
     def to_all_tensors(self, op, target, source, PE_start=0, logPE_stride=0, PE_size=None):
         """shmem_<T>_<op>_to_all on two contiguous device tensors of one dtype
-        (T from the tensor's dtype; long double has no torch dtype). They need
+        (T from the tensor's dtype; long double has no torch dtype;
+        torch.float16 and torch.bfloat16 take shmemx_half_* / shmemx_bfloat16_*:
+        sum, prod, min, max, every step rounded to the type). They need
         not come from the symmetric heap: at PE_size > 1 the members map each
         other's allocations for the call (shmemx.h, extmap.c). Blocking, like
         the C call: on return `target` holds this PE's result."""
@@ -360,7 +382,8 @@ class Shmem:
         name = TORCH_DTYPES.get(str(dtype).replace("torch.", ""))
         if name is None:
             raise TypeError(f"no shmem_*_to_all for {dtype}")
-        np_dt = np.dtype(NP[name])
+        # bfloat16 has no array-interface type string: wrapped as 16-bit integers, viewed below
+        np_dt = np.dtype(np.int16 if name == "bfloat16" else NP[name])
         ptr = self.malloc_device(max(1, n) * np_dt.itemsize)
         if not ptr:
             raise MemoryError("device symmetric heap exhausted")
@@ -372,13 +395,13 @@ class Shmem:
         t = torch.as_tensor(_HeapBuffer(), device=f"cuda:{self.lib.shmemx_device_id()}")
         if t.data_ptr() != ptr:
             raise RuntimeError("torch copied the heap buffer instead of wrapping it")
-        return t
+        return t if t.dtype == dtype else t.view(dtype)   # bfloat16: wrapped as its 16-bit patterns
 
     def _stream_reduction(self, op, dtype):
         key = ("stream", op, dtype)
         f = self._fns.get(key)
         if f is None:
-            f = getattr(self.lib, f"shmemx_{dtype}_{op}_to_all_on_stream")
+            f = getattr(self.lib, f"shmemx_{dtype}_{op}_to_all_on_stream")   # the 16-bit floats' too
             f.restype = None
             f.argtypes = [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]
             self._fns[key] = f
