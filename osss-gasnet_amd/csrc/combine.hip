@@ -347,43 +347,20 @@ static int copy_segments_impl(void *const *dsts, const void *const *srcs, const 
 static int combine_orders_impl(int op, int dtype, void *const *dsts, const void *const *srcs, int nsrc, size_t n,
                                void *stream);
 
-// mi355_copy_direction_next_launch: > 0 ascending, < 0 descending, 0: none
-// (single-segment copies alternate, next_copy_descends)
-static thread_local int t_copy_dir = 0;
-
-// Every error return cancels an armed signal/timing/direction request (nothing carries them).
+// Every entry point returns through LaunchState::end_call (combine_kernels.h): what each consumes and cancels.
 extern "C" int mi355_combine(int op, int dtype, void *dst, const void *const *srcs, int nsrc,
                              size_t n, void *stream) {
-    const int rc = combine_impl(op, dtype, dst, srcs, nsrc, n, stream);
-    t_nan_set = t_nan_clear = nullptr;  // a call that launched no fold consumes them too
-    if (rc != 0) {
-        t_sig = Signal{nullptr, nullptr, 0};
-        t_ev_start = t_ev_stop = nullptr;
-        t_copy_dir = 0;
-    }
-    return rc;
+    return t_launch.end_call(combine_impl(op, dtype, dst, srcs, nsrc, n, stream), ARMED_NAN, ARMED_DIR);
 }
 
 extern "C" int mi355_combine_orders(int op, int dtype, void *const *dsts, const void *const *srcs, int nsrc,
                                     size_t n, void *stream) {
-    const int rc = combine_orders_impl(op, dtype, dsts, srcs, nsrc, n, stream);
-    if (rc != 0) {
-        t_sig = Signal{nullptr, nullptr, 0};
-        t_ev_start = t_ev_stop = nullptr;
-        t_copy_dir = 0;
-    }
-    return rc;
+    return t_launch.end_call(combine_orders_impl(op, dtype, dsts, srcs, nsrc, n, stream), 0, ARMED_DIR);
 }
 
 extern "C" int mi355_copy_segments(void *const *dsts, const void *const *srcs, const size_t *nbytes,
                                    int nseg, void *stream) {
-    const int rc = copy_segments_impl(dsts, srcs, nbytes, nseg, stream);
-    t_copy_dir = 0;  // a multi-segment launch (always ascending) or a call with nothing to copy consumes it too
-    if (rc != 0) {
-        t_sig = Signal{nullptr, nullptr, 0};
-        t_ev_start = t_ev_stop = nullptr;
-    }
-    return rc;
+    return t_launch.end_call(copy_segments_impl(dsts, srcs, nbytes, nseg, stream), ARMED_DIR);
 }
 
 static int combine_impl(int op, int dtype, void *dst, const void *const *srcs, int nsrc, size_t n,
@@ -468,8 +445,8 @@ static int combine_orders_impl(int op, int dtype, void *const *dsts, const void 
 static std::atomic<unsigned> g_copy_descended{1};
 
 static bool next_copy_descends() {
-    const int pin = t_copy_dir;
-    t_copy_dir = 0;
+    const int pin = t_launch.copy_dir;
+    t_launch.copy_dir = 0;
     if (pin != 0) {
         g_copy_descended.store(pin < 0 ? 1u : 0u, std::memory_order_relaxed);
         return pin < 0;
@@ -542,11 +519,11 @@ static int copy_segments_impl(void *const *dsts, const void *const *srcs, const 
                   (hipStream_t)stream, p);
 }
 
-extern "C" void mi355_copy_direction_next_launch(int dir) { t_copy_dir = dir; }
+extern "C" void mi355_copy_direction_next_launch(int dir) { t_launch.copy_dir = dir; }
 
 extern "C" void mi355_nan_flag_next_launch(unsigned long long *set, unsigned long long *clear) {
-    t_nan_set = set;
-    t_nan_clear = clear;
+    t_launch.nan_set = set;
+    t_launch.nan_clear = clear;
 }
 
 extern "C" int mi355_nan_patch_copy(int dtype, void *dst, const void *peer, const void *own, size_t n,
@@ -564,7 +541,7 @@ extern "C" int mi355_nan_patch_copy(int dtype, void *dst, const void *peer, cons
         // by element when dst and peer differ in phase or dst is not
         // element-aligned.
         // dst is peeled to its 128-byte line (whole-line stores, see
-        // combine_kernels.h vector_head) when n reaches it, else to 16 bytes.
+        // launch_plan.h) when n reaches it, else to 16 bytes.
         const uintptr_t pd = (uintptr_t)dst & 15;
         const bool vec = pd == ((uintptr_t)peer & 15) && pd % es == 0;
         const size_t lh = ((128 - ((uintptr_t)dst & 127)) & 127) / es;
@@ -591,11 +568,7 @@ extern "C" int mi355_nan_patch_copy(int dtype, void *dst, const void *peer, cons
                                       : (shift ? nan_patch_copy<double, true> : nan_patch_copy<double, false>);
         return launch(k, dim3(grid), (hipStream_t)stream, p);
     }();
-    if (rc != 0) {
-        t_sig = Signal{nullptr, nullptr, 0};
-        t_ev_start = t_ev_stop = nullptr;
-    }
-    return rc;
+    return t_launch.end_call(rc);
 }
 
 // System-scope acquire on every XCD of this GPU (`buffer_inv sc0 sc1`): drops
@@ -622,37 +595,37 @@ extern "C" int mi355_acquire_system(void *stream) {
 }
 
 extern "C" int mi355_signal_launch(void *stream) {
-    if (t_sig.flag == nullptr) return MI355_E_INVAL;
+    if (t_launch.sig.flag == nullptr) return MI355_E_INVAL;
     return launch(signal_only, dim3(1), (hipStream_t)stream, EmptyParams{});
 }
 
 extern "C" void mi355_signal_next_launch(unsigned *count, unsigned *flag, unsigned epoch) {
-    t_sig = Signal{count, flag, epoch};
+    t_launch.sig = Signal{count, flag, epoch};
 }
 
 extern "C" void mi355_time_next_launch(void *start_event, void *stop_event) {
-    t_ev_start = (hipEvent_t)start_event;
-    t_ev_stop = (hipEvent_t)stop_event;
+    t_launch.ev_start = (hipEvent_t)start_event;
+    t_launch.ev_stop = (hipEvent_t)stop_event;
 }
 
 // For fused.hip (same library): take the event pair armed for the next
 // launch, if any, so its kernels carry the stamps too.
 extern "C" void mi355i_take_launch_events(void **start_event, void **stop_event) {
-    *start_event = t_ev_start;
-    *stop_event = t_ev_stop;
-    t_ev_start = t_ev_stop = nullptr;
+    *start_event = t_launch.ev_start;
+    *stop_event = t_launch.ev_stop;
+    t_launch.ev_start = t_launch.ev_stop = nullptr;
 }
 
 // For fused.hip: its launches count as this layer's last kernel too.
-extern "C" void mi355i_note_launch(const void *kernel) { t_last_kernel = kernel; }
+extern "C" void mi355i_note_launch(const void *kernel) { t_launch.last_kernel = kernel; }
 
-extern "C" const void *mi355_last_kernel(void) { return t_last_kernel; }
+extern "C" const void *mi355_last_kernel(void) { return t_launch.last_kernel; }
 
 extern "C" int mi355_device_cus(void) { return device_cus(); }
 
 extern "C" void mi355_last_launch_grid(unsigned *gx, unsigned *gy) {
-    if (gx != nullptr) *gx = t_last_grid[0];
-    if (gy != nullptr) *gy = t_last_grid[1];
+    if (gx != nullptr) *gx = t_launch.last_grid[0];
+    if (gy != nullptr) *gy = t_launch.last_grid[1];
 }
 
 // The kernel's demangled name, as rocprofv3 prints it ("void

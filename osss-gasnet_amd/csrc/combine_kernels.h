@@ -11,7 +11,9 @@
 #include <atomic>
 #include <mutex>
 #include <type_traits>
+#include <utility>
 
+#include "launch_plan.h"
 #include "mi355_reduce.h"
 #include "ops.h"
 
@@ -556,39 +558,75 @@ __global__ __launch_bounds__(kBlock) void combine_orders_scalar(OrdersParams p) 
 // ---------------------------------------------------------------------------
 inline int g_cus[64];
 
-// events and completion signal for the next launch (mi355_time_next_launch,
-// mi355_signal_next_launch), consumed by it
-inline thread_local hipEvent_t t_ev_start = nullptr, t_ev_stop = nullptr;
-inline thread_local Signal t_sig = {nullptr, nullptr, 0};
-// host stub of the kernel this layer launched last (mi355_last_kernel)
-inline thread_local const void *t_last_kernel = nullptr;
-// ... and its grid (mi355_last_launch_grid)
-inline thread_local unsigned t_last_grid[2] = {0, 0};
-// NaN words for the next fold (mi355_nan_flag_next_launch), consumed by it
-inline thread_local unsigned long long *t_nan_set = nullptr, *t_nan_clear = nullptr;
+// What a caller armed for this thread's next launch, and what this thread
+// launched last: the one owner of that state. Who takes what:
+//   launch()              the event pair, always; the signal when the launch
+//                         is the call's `final` one (earlier launches of a
+//                         multi-launch call run unsignalled); it records the
+//                         kernel and grid. fused.hip's launches reach the
+//                         events and the record through mi355i_take_launch_events
+//                         and mi355i_note_launch only.
+//   launch_fixed()        the NaN words, before anything else: the k-source
+//                         fold is the only kernel that carries them
+//   next_copy_descends()  the direction pin (combine.hip: single-segment copies)
+//   fire_on_host()        a call with nothing to launch fires the signal from
+//                         the host and takes it; the events stay armed for the
+//                         next launch
+//   end_call()            every entry point returns through it: `spent` names
+//                         what the entry consumes even when it launched
+//                         nothing or another kernel than the one that carries
+//                         it; an error return also cancels the signal, the
+//                         events and `on_error` (nothing will carry them).
+//                         mi355_combine: the NaN words spent, the pin dropped
+//                         on error; mi355_combine_orders: the pin dropped on
+//                         error; mi355_copy_segments: the pin spent (a
+//                         multi-segment launch always ascends);
+//                         mi355_nan_patch_copy and the strided copies: neither.
+enum { ARMED_NAN = 1, ARMED_DIR = 2 };
+struct LaunchState {
+    Signal sig = {nullptr, nullptr, 0};                  // mi355_signal_next_launch
+    hipEvent_t ev_start = nullptr, ev_stop = nullptr;    // mi355_time_next_launch
+    unsigned long long *nan_set = nullptr, *nan_clear = nullptr;   // mi355_nan_flag_next_launch
+    int copy_dir = 0;   // mi355_copy_direction_next_launch: > 0 ascending, < 0 descending, 0: none
+    const void *last_kernel = nullptr;   // host stub of the kernel launched last (mi355_last_kernel)
+    unsigned last_grid[2] = {0, 0};      // ... and its grid (mi355_last_launch_grid)
+
+    int end_call(int rc, unsigned spent = 0, unsigned on_error = 0) {
+        if (rc != 0) {
+            sig = Signal{nullptr, nullptr, 0};
+            ev_start = ev_stop = nullptr;
+            spent |= on_error;
+        }
+        if (spent & ARMED_NAN) nan_set = nan_clear = nullptr;
+        if (spent & ARMED_DIR) copy_dir = 0;
+        return rc;
+    }
+};
+inline thread_local LaunchState t_launch;
 
 // A host-visible word the host can also write: an armed signal that no kernel
 // will carry (nothing to launch) is fired right here, in stream order.
 inline void fire_on_host(hipStream_t st) {
-    if (t_sig.flag == nullptr) return;
-    if (hipStreamSynchronize(st) == hipSuccess)
-        __atomic_store_n(t_sig.flag, t_sig.epoch, __ATOMIC_RELEASE);
-    t_sig = Signal{nullptr, nullptr, 0};
+    Signal &sig = t_launch.sig;
+    if (sig.flag == nullptr) return;
+    if (hipStreamSynchronize(st) == hipSuccess) __atomic_store_n(sig.flag, sig.epoch, __ATOMIC_RELEASE);
+    sig = Signal{nullptr, nullptr, 0};
 }
 
 // `final`: the last launch of an API call, the one that carries the signal
 template <typename K, typename P>
 int launch(K kernel, dim3 grid, hipStream_t st, P p, bool final = true) {
+    LaunchState &s = t_launch;
     p.sig = Signal{nullptr, nullptr, 0};
     if (final) {
-        p.sig = t_sig;
-        t_sig = Signal{nullptr, nullptr, 0};
+        p.sig = s.sig;
+        s.sig = Signal{nullptr, nullptr, 0};
     }
-    t_last_kernel = (const void *)kernel;
-    t_last_grid[0] = grid.x, t_last_grid[1] = grid.y;
-    if (t_ev_start != nullptr || t_ev_stop != nullptr) {
-        hipExtLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, st, t_ev_start, t_ev_stop, 0, p);
-        t_ev_start = t_ev_stop = nullptr;
+    s.last_kernel = (const void *)kernel;
+    s.last_grid[0] = grid.x, s.last_grid[1] = grid.y;
+    if (s.ev_start != nullptr || s.ev_stop != nullptr) {
+        hipExtLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, st, s.ev_start, s.ev_stop, 0, p);
+        s.ev_start = s.ev_stop = nullptr;
     } else {
         hipLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, st, p);
     }
@@ -731,121 +769,65 @@ template <int OP, int NSRC, typename T> struct OrdersShape {
     static constexpr int policy = POL_NT_LOAD;
 };
 
-// Elements to peel so that every output starts on a 128-byte line, when the
-// outputs share their offset within one (the symmetric target on each PE)
-// and n reaches past it; else so that they start on 16 bytes. Outputs off
-// their line store partial lines at both ends of every wave's span: a fold
-// or copy whose target sits 16 bytes off its line ran 3-25 % slower warm and
-// up to 30 % slower from HBM (profiles/r05/cold/linepeel_*.jsonl). pd: the
-// outputs' common phase within 16 bytes (a multiple of the element size).
-// 16-byte elements: no head (the kernels fold a head only for V > 1).
-template <typename T>
-size_t line_head(const void *const *outs, int nout, uintptr_t pd, size_t n) {
-    if (sizeof(T) >= 16) return 0;
-    const uintptr_t pl = (uintptr_t)outs[0] & 127;
-    bool line = true;
-    for (int k = 1; k < nout; ++k) line = line && ((uintptr_t)outs[k] & 127) == pl;
-    const size_t h = ((128 - pl) & 127) / sizeof(T);
-    return line && n > h ? h : ((16 - pd) & 15) / sizeof(T);
+// A run-time v in [Lo, Hi] as a compile-time constant: f(std::integral_constant<int, v>),
+// MI355_E_INVAL outside the range. One instantiation of f per value. Compared
+// from Hi down: the compiler then emits the kernels those instantiations name
+// in ascending order, as the switch ladders this replaces did, which keeps
+// each translation unit's device code byte for byte what it was.
+template <int Hi, typename F, int... I>
+int with_constant(int v, F &&f, std::integer_sequence<int, I...>) {
+    int rc = MI355_E_INVAL;
+    (void)((v == Hi - I && (rc = f(std::integral_constant<int, Hi - I>{}), true)) || ...);
+    return rc;
+}
+template <int Lo, int Hi, typename F>
+int with_constant(int v, F &&f) {
+    return with_constant<Hi>(v, f, std::make_integer_sequence<int, Hi - Lo + 1>{});
 }
 
-// How a launch over these pointers can run as 16-byte vectors: h >= 0 =
-// every pointer at one phase within 16 bytes, by whole elements (0 or a user
-// offset into the arrays): fold the first h elements (line_head) element-wise
-// and the rest as vectors from the advanced pointers; -1 = not vectorisable
-// this way (shift_head below, else the element-wise kernel).
-template <typename T>
-long vector_head(const void *const *outs, int nout, const void *const *ins, int nin, size_t n) {
-    constexpr int V = 16 / sizeof(T);
-    const uintptr_t pd = (uintptr_t)(nout > 0 ? outs[0] : ins[0]) & 15;
-    bool same = pd % sizeof(T) == 0;
-    for (int k = 0; k < nout; ++k) same = same && ((uintptr_t)outs[k] & 15) == pd;
-    for (int k = 0; k < nin; ++k) same = same && ((uintptr_t)ins[k] & 15) == pd;
-    if (!same) return -1;
-    if (V == 1 || nout == 0) return pd == 0 ? 0 : -1;
-    const size_t head = line_head<T>(outs, nout, pd, n);
-    if (head == 0 || n > head) return (long)head;
-    return pd == 0 ? 0 : -1;
+// The plan (launch_plan.h) into a params struct: the vector counts, and every
+// pointer advanced past the head (a null output stays null).
+template <typename P>
+void apply_plan(P &p, void **dsts, int ndst, int nsrc, const LaunchPlan &plan, size_t es) {
+    p.head = (uint32_t)plan.head;
+    p.nvec = plan.nvec;
+    p.tail = (uint32_t)plan.tail;
+    for (int k = 0; k < ndst; ++k)
+        if (dsts[k] != nullptr) dsts[k] = (char *)dsts[k] + plan.head * es;
+    for (int k = 0; k < nsrc; ++k) p.src[k] = (const char *)p.src[k] + plan.head * es;
 }
 
-// Outputs 16-byte aligned after peeling whole elements and the sources at
-// any phases, one or several (an offset into some of the arrays): the vector
-// kernels with unaligned source loads (SHIFT; an unaligned-form load of an
-// aligned address is the same instruction). Returns the elements to peel,
-// or -1 (outputs at different phases or not element-aligned, no whole
-// vector, long double). The aligned launch shapes (cold_probe unal: the
-// same rates at 2 or 4 blocks per CU).
-template <typename T>
-long shift_head(const void *const *outs, int nout, const void *const *srcs, int nsrc, size_t n) {
-    if constexpr (std::is_same<T, x80>::value) {
-        return -1;
-    } else {
-        constexpr size_t es = sizeof(T);
-        constexpr size_t V = 16 / es;
-        const uintptr_t pd = (uintptr_t)outs[0] & 15;
-        for (int k = 1; k < nout; ++k)
-            if (((uintptr_t)outs[k] & 15) != pd) return -1;
-        if (pd % es != 0) return -1;
-        const size_t head = line_head<T>(outs, nout, pd, n);
-        bool aligned = true;
-        for (int k = 0; k < nsrc; ++k) aligned = aligned && (((uintptr_t)srcs[k] + head * es) & 15) == 0;
-        if (aligned || n < head + V) return -1;
-        return (long)head;
-    }
-}
+// One launch of the k-source fold, NSRC <= kMaxSrc: plan, kernel, grid.
 template <int OP, typename T, int NSRC>
 int launch_fixed(void *dst, const void *const *srcs, size_t n, hipStream_t st, bool final) {
+    constexpr bool shiftable = !std::is_same<T, x80>::value;
+    using S = ShapeOp<OP, NSRC, T>;
     CombineParams p{};
-    p.nan_set = t_nan_set;
-    p.nan_clear = t_nan_clear;
-    t_nan_set = t_nan_clear = nullptr;
-    const void *ptrs[kMaxSrc + 1];
+    p.nan_set = t_launch.nan_set;
+    p.nan_clear = t_launch.nan_clear;
+    t_launch.nan_set = t_launch.nan_clear = nullptr;
     p.dst = dst;
-    ptrs[0] = dst;
-    for (int k = 0; k < NSRC; ++k) p.src[k] = ptrs[1 + k] = srcs[k];
-    constexpr int V = 16 / sizeof(T);
-    const long head = vector_head<T>(&ptrs[0], 1, &ptrs[1], NSRC, n);
-    if (head >= 0) {
-        if (head > 0) {
-            p.head = (uint32_t)head;
-            p.dst = (char *)dst + head * sizeof(T);
-            for (int k = 0; k < NSRC; ++k) p.src[k] = (const char *)srcs[k] + head * sizeof(T);
-            n -= (size_t)head;
-        }
-        using S = ShapeOp<OP, NSRC, T>;
-        p.nvec = n / V;
-        p.tail = (uint32_t)(n % V);
-        auto k = combine_vec<OP, T, NSRC, S::unroll, S::policy>;
-        const int bpc = !S::alu_heavy || S::blocks_per_cu < resident_blocks((const void *)k)
-                            ? S::blocks_per_cu
-                            : resident_blocks((const void *)k);
-        const unsigned grid = grid_for((uint64_t)kBlock * S::unroll, p.nvec, bpc);
-        return launch(k, dim3(grid), st, p, final);
+    for (int k = 0; k < NSRC; ++k) p.src[k] = srcs[k];
+    const void *out = dst;
+    const LaunchPlan plan = plan_launch(sizeof(T), shiftable, &out, 1, srcs, NSRC, n);
+    apply_plan(p, &p.dst, 1, NSRC, plan, sizeof(T));
+    void (*k)(CombineParams) = combine_vec<OP, T, NSRC, S::unroll, S::policy>;
+    if constexpr (shiftable) {
+        if (plan.kind == PLAN_SHIFT) k = combine_vec<OP, T, NSRC, S::unroll, S::policy, true>;
     }
-    const long sh = shift_head<T>(&ptrs[0], 1, &ptrs[1], NSRC, n);
-    if constexpr (!std::is_same<T, x80>::value) {
-        if (sh >= 0) {
-            p.head = (uint32_t)sh;
-            p.dst = (char *)dst + sh * sizeof(T);
-            for (int k = 0; k < NSRC; ++k) p.src[k] = (const char *)srcs[k] + sh * sizeof(T);
-            n -= (size_t)sh;
-            using S = ShapeOp<OP, NSRC, T>;
-            p.nvec = n / V;
-            p.tail = (uint32_t)(n % V);
-            auto k = combine_vec<OP, T, NSRC, S::unroll, S::policy, true>;
-            const unsigned grid = grid_for((uint64_t)kBlock * S::unroll, p.nvec, S::blocks_per_cu);
-            return launch(k, dim3(grid), st, p, final);
-        }
-    }
-    p.nvec = n;
-    p.tail = 0;
-    const unsigned grid = grid_for((uint64_t)kBlock * 4, n);
-    return launch(combine_scalar<OP, T, NSRC>, dim3(grid), st, p, final);
+    if (plan.kind == PLAN_ELEMENTS)
+        return launch(combine_scalar<OP, T, NSRC>, dim3(grid_for((uint64_t)kBlock * 4, n)), st, p, final);
+    // the residency cap: ALU-heavy shapes only (long double, which never takes SHIFT)
+    int bpc = S::blocks_per_cu;
+    if (S::alu_heavy && resident_blocks((const void *)k) < bpc) bpc = resident_blocks((const void *)k);
+    return launch(k, dim3(grid_for((uint64_t)kBlock * S::unroll, p.nvec, bpc)), st, p, final);
 }
 
 // mi355_combine_orders for NSRC <= kMaxSrc sources: one launch
 template <int OP, typename T, int NSRC>
 int launch_orders_fixed(void *const *dsts, const void *const *srcs, size_t n, hipStream_t st) {
+    constexpr bool shiftable = !std::is_same<T, x80>::value;
+    using S = OrdersShape<OP, NSRC, T>;
     OrdersParams p{};
     const void *outs[kMaxSrc];
     int nout = 0;
@@ -854,75 +836,39 @@ int launch_orders_fixed(void *const *dsts, const void *const *srcs, size_t n, hi
         p.dst[k] = dsts[k];
         if (dsts[k] != nullptr) outs[nout++] = dsts[k];
     }
-    constexpr int V = 16 / sizeof(T);
-    const long head = vector_head<T>(outs, nout, srcs, NSRC, n);
-    if (head >= 0) {
-        if (head > 0) {
-            p.head = (uint32_t)head;
-            for (int k = 0; k < NSRC; ++k) {
-                p.src[k] = (const char *)srcs[k] + head * sizeof(T);
-                if (dsts[k] != nullptr) p.dst[k] = (char *)dsts[k] + head * sizeof(T);
-            }
-            n -= (size_t)head;
-        }
-        using S = OrdersShape<OP, NSRC, T>;
-        p.nvec = n / V;
-        p.tail = (uint32_t)(n % V);
-        bool all = true;
-        for (int k = 0; k < NSRC; ++k) all = all && dsts[k] != nullptr;
-        auto k = all ? combine_orders_vec<OP, T, NSRC, S::unroll, S::policy, true>
-                     : combine_orders_vec<OP, T, NSRC, S::unroll, S::policy, false>;
-        int bpc = !S::alu_heavy || S::blocks_per_cu < resident_blocks((const void *)k)
-                      ? S::blocks_per_cu
-                      : resident_blocks((const void *)k);
-        // the measured ALU-heavy folds -- x87 sum/product, float complex
-        // product (profiles/r04/alu_grid/) -- one vector per lane, every
-        // block queued at once, so the hardware hands out the last round's
-        // work as slots free instead of a resident grid's fixed rounds
-        if ((S::alu_heavy && (OP == MI355_OP_SUM || OP == MI355_OP_PROD)) ||
-            (std::is_same<T, cplxf>::value && OP == MI355_OP_PROD))
-            bpc = 1 << 20;
-        const unsigned grid = grid_for((uint64_t)kBlock * S::unroll, p.nvec, bpc);
-        return launch(k, dim3(grid), st, p);
+    const LaunchPlan plan = plan_launch(sizeof(T), shiftable, outs, nout, srcs, NSRC, n);
+    apply_plan(p, p.dst, NSRC, NSRC, plan, sizeof(T));
+    const bool all = nout == NSRC;   // ALL: every dst non-null
+    void (*k)(OrdersParams) = all ? combine_orders_vec<OP, T, NSRC, S::unroll, S::policy, true>
+                                  : combine_orders_vec<OP, T, NSRC, S::unroll, S::policy, false>;
+    if constexpr (shiftable) {
+        if (plan.kind == PLAN_SHIFT)
+            k = all ? combine_orders_vec<OP, T, NSRC, S::unroll, S::policy, true, true>
+                    : combine_orders_vec<OP, T, NSRC, S::unroll, S::policy, false, true>;
     }
-    const long sh = nout > 0 ? shift_head<T>(outs, nout, srcs, NSRC, n) : -1;
-    if constexpr (!std::is_same<T, x80>::value) {
-        if (sh >= 0) {
-            p.head = (uint32_t)sh;
-            for (int k = 0; k < NSRC; ++k) {
-                p.src[k] = (const char *)srcs[k] + sh * sizeof(T);
-                if (dsts[k] != nullptr) p.dst[k] = (char *)dsts[k] + sh * sizeof(T);
-            }
-            n -= (size_t)sh;
-            using S = OrdersShape<OP, NSRC, T>;
-            p.nvec = n / V;
-            p.tail = (uint32_t)(n % V);
-            const bool all = nout == NSRC;
-            auto k = all ? combine_orders_vec<OP, T, NSRC, S::unroll, S::policy, true, true>
-                         : combine_orders_vec<OP, T, NSRC, S::unroll, S::policy, false, true>;
-            const unsigned grid = grid_for((uint64_t)kBlock * S::unroll, p.nvec, S::blocks_per_cu);
-            return launch(k, dim3(grid), st, p);
-        }
-    }
-    p.nvec = n;
-    p.tail = 0;
-    const unsigned grid = grid_for((uint64_t)kBlock * 4, n);
-    return launch(combine_orders_scalar<OP, T, NSRC>, dim3(grid), st, p);
+    if (plan.kind == PLAN_ELEMENTS)
+        return launch(combine_orders_scalar<OP, T, NSRC>, dim3(grid_for((uint64_t)kBlock * 4, n)), st, p);
+    // the residency cap: ALU-heavy shapes only (long double, which never takes SHIFT)
+    int bpc = S::blocks_per_cu;
+    if (S::alu_heavy && resident_blocks((const void *)k) < bpc) bpc = resident_blocks((const void *)k);
+    // the measured ALU-heavy folds -- x87 sum/product, float complex
+    // product (profiles/r04/alu_grid/) -- one vector per lane, every
+    // block queued at once, so the hardware hands out the last round's
+    // work as slots free instead of a resident grid's fixed rounds.
+    // ALIGNED only: the float complex product's SHIFT launch has always kept
+    // S::blocks_per_cu. That may be an oversight of the shifted kernels'
+    // introduction; it stays until a measurement says otherwise (a tuning
+    // change, not a refactoring).
+    if (plan.kind == PLAN_ALIGNED && ((S::alu_heavy && (OP == MI355_OP_SUM || OP == MI355_OP_PROD)) ||
+                                      (std::is_same<T, cplxf>::value && OP == MI355_OP_PROD)))
+        bpc = 1 << 20;
+    return launch(k, dim3(grid_for((uint64_t)kBlock * S::unroll, p.nvec, bpc)), st, p);
 }
 
 template <int OP, typename T>
 int launch_n(int nsrc, void *dst, const void *const *srcs, size_t n, hipStream_t st, bool final) {
-    switch (nsrc) {
-    case 1: return launch_fixed<OP, T, 1>(dst, srcs, n, st, final);
-    case 2: return launch_fixed<OP, T, 2>(dst, srcs, n, st, final);
-    case 3: return launch_fixed<OP, T, 3>(dst, srcs, n, st, final);
-    case 4: return launch_fixed<OP, T, 4>(dst, srcs, n, st, final);
-    case 5: return launch_fixed<OP, T, 5>(dst, srcs, n, st, final);
-    case 6: return launch_fixed<OP, T, 6>(dst, srcs, n, st, final);
-    case 7: return launch_fixed<OP, T, 7>(dst, srcs, n, st, final);
-    case 8: return launch_fixed<OP, T, 8>(dst, srcs, n, st, final);
-    default: return MI355_E_INVAL;
-    }
+    return with_constant<1, kMaxSrc>(
+        nsrc, [&](auto k) { return launch_fixed<OP, T, decltype(k)::value>(dst, srcs, n, st, final); });
 }
 
 // Left fold of any number of sources: first kMaxSrc into dst, then dst
@@ -950,16 +896,8 @@ int launch_fold(void *dst, const void *const *srcs, int nsrc, size_t n, hipStrea
 
 template <typename T>
 int dispatch_op(int op, void *dst, const void *const *srcs, int nsrc, size_t n, hipStream_t st) {
-    switch (op) {
-    case MI355_OP_SUM: return launch_fold<MI355_OP_SUM, T>(dst, srcs, nsrc, n, st);
-    case MI355_OP_PROD: return launch_fold<MI355_OP_PROD, T>(dst, srcs, nsrc, n, st);
-    case MI355_OP_AND: return launch_fold<MI355_OP_AND, T>(dst, srcs, nsrc, n, st);
-    case MI355_OP_OR: return launch_fold<MI355_OP_OR, T>(dst, srcs, nsrc, n, st);
-    case MI355_OP_XOR: return launch_fold<MI355_OP_XOR, T>(dst, srcs, nsrc, n, st);
-    case MI355_OP_MIN: return launch_fold<MI355_OP_MIN, T>(dst, srcs, nsrc, n, st);
-    case MI355_OP_MAX: return launch_fold<MI355_OP_MAX, T>(dst, srcs, nsrc, n, st);
-    default: return MI355_E_INVAL;
-    }
+    return with_constant<0, MI355_NUM_OPS - 1>(
+        op, [&](auto o) { return launch_fold<decltype(o)::value, T>(dst, srcs, nsrc, n, st); });
 }
 
 // Every member's order (mi355_combine_orders): one launch up to kMaxSrc
@@ -971,16 +909,9 @@ int launch_orders(void *const *dsts, const void *const *srcs, int nsrc, size_t n
     if constexpr (!valid_pair<OP, T>()) {
         return MI355_E_UNSUP;
     } else {
-        switch (nsrc) {
-        case 2: return launch_orders_fixed<OP, T, 2>(dsts, srcs, n, st);
-        case 3: return launch_orders_fixed<OP, T, 3>(dsts, srcs, n, st);
-        case 4: return launch_orders_fixed<OP, T, 4>(dsts, srcs, n, st);
-        case 5: return launch_orders_fixed<OP, T, 5>(dsts, srcs, n, st);
-        case 6: return launch_orders_fixed<OP, T, 6>(dsts, srcs, n, st);
-        case 7: return launch_orders_fixed<OP, T, 7>(dsts, srcs, n, st);
-        case 8: return launch_orders_fixed<OP, T, 8>(dsts, srcs, n, st);
-        default: break;
-        }
+        if (nsrc >= 2 && nsrc <= kMaxSrc)
+            return with_constant<2, kMaxSrc>(
+                nsrc, [&](auto k) { return launch_orders_fixed<OP, T, decltype(k)::value>(dsts, srcs, n, st); });
         int alias = -1, last = -1;
         for (int q = 0; q < nsrc; ++q) {
             if (dsts[q] == nullptr) continue;
@@ -1005,16 +936,8 @@ int launch_orders(void *const *dsts, const void *const *srcs, int nsrc, size_t n
 
 template <typename T>
 int dispatch_orders(int op, void *const *dsts, const void *const *srcs, int nsrc, size_t n, hipStream_t st) {
-    switch (op) {
-    case MI355_OP_SUM: return launch_orders<MI355_OP_SUM, T>(dsts, srcs, nsrc, n, st);
-    case MI355_OP_PROD: return launch_orders<MI355_OP_PROD, T>(dsts, srcs, nsrc, n, st);
-    case MI355_OP_AND: return launch_orders<MI355_OP_AND, T>(dsts, srcs, nsrc, n, st);
-    case MI355_OP_OR: return launch_orders<MI355_OP_OR, T>(dsts, srcs, nsrc, n, st);
-    case MI355_OP_XOR: return launch_orders<MI355_OP_XOR, T>(dsts, srcs, nsrc, n, st);
-    case MI355_OP_MIN: return launch_orders<MI355_OP_MIN, T>(dsts, srcs, nsrc, n, st);
-    case MI355_OP_MAX: return launch_orders<MI355_OP_MAX, T>(dsts, srcs, nsrc, n, st);
-    default: return MI355_E_INVAL;
-    }
+    return with_constant<0, MI355_NUM_OPS - 1>(
+        op, [&](auto o) { return launch_orders<decltype(o)::value, T>(dsts, srcs, nsrc, n, st); });
 }
 
 // One element type's entry points, defined by combine_t_<name>.hip

@@ -250,24 +250,14 @@ static int strided_copy_impl(int elem_size, void *const *dsts, const void *const
     }
 }
 
-// Every error return cancels an armed signal/timing request, as in combine.hip.
-static int strided_cancel_on_error(int rc) {
-    if (rc != 0) {
-        t_sig = Signal{nullptr, nullptr, 0};
-        t_ev_start = t_ev_stop = nullptr;
-    }
-    return rc;
-}
-
 extern "C" int mi355_strided_copy(int elem_size, void *const *dsts, const void *const *srcs, ptrdiff_t dst_stride,
                                   ptrdiff_t src_stride, size_t nelems, int nseg, void *stream) {
-    return strided_cancel_on_error(
-        strided_copy_impl(elem_size, dsts, srcs, dst_stride, src_stride, nelems, nseg, stream));
+    return t_launch.end_call(strided_copy_impl(elem_size, dsts, srcs, dst_stride, src_stride, nelems, nseg, stream));
 }
 
 // The all-to-all's front: 4- and 8-byte elements only, the same launches.
 extern "C" int mi355_strided_pull(int elem_size, void *const *dsts, const void *const *srcs, ptrdiff_t dst_stride,
                                   ptrdiff_t src_stride, size_t nelems, int nseg, void *stream) {
-    if (elem_size != 4 && elem_size != 8) return strided_cancel_on_error(MI355_E_INVAL);
+    if (elem_size != 4 && elem_size != 8) return t_launch.end_call(MI355_E_INVAL);
     return mi355_strided_copy(elem_size, dsts, srcs, dst_stride, src_stride, nelems, nseg, stream);
 }

@@ -724,3 +724,195 @@ def test_nan_patch_copy_phases_and_flag(shm, dev, dtype):
                 assert (got == want).all(), (doff, ooff, n, flag, int(np.argmax(got != want)))
             dev.free()
             words = {v: _upload_at(dev, np.array([v], np.uint64), 0) for v in (0, 1)}
+
+
+# ---------------------------------------------------------------------------
+# Launch identity: which kernel and which grid the launchers pick for a given
+# set of pointers (csrc/launch_plan.h plans, combine_kernels.h launches),
+# against a table recorded on the GPU from the build before the launchers were
+# rewritten around the plan (tests/golden/launch_identity.json).
+# ---------------------------------------------------------------------------
+def _launch_layouts(es):
+    """name -> (target byte offset, source k's byte offset); every buffer starts 256-byte aligned"""
+    sh = es if es < 16 else 8
+    return {"aligned": (0, lambda k: 0),        # ALIGNED, no head
+            "off8": (sh, lambda k: sh),         # ALIGNED after a head (every pointer one element off)
+            "shift": (sh, lambda k: 0),         # target = &t[1] over source = &s[0]: SHIFT (long double: ELEMENTS)
+            "mixed": (0, lambda k: (k % 2) * sh)}   # sources at two phases: SHIFT
+
+
+# (id, call, op, dtype, sources, n, layout, skipped outputs). head: the line
+# head of "off8"/"shift" is (128 - es) / es elements.
+LAUNCH_CASES = [
+    ("fold short sum 2 aligned", "fold", "sum", "short", 2, 4099, "aligned", ()),
+    ("fold float sum 2 aligned", "fold", "sum", "float", 2, 4099, "aligned", ()),
+    ("fold double sum 3 aligned", "fold", "sum", "double", 3, 4099, "aligned", ()),
+    ("fold longdouble sum 2 aligned", "fold", "sum", "longdouble", 2, 1031, "aligned", ()),
+    ("fold complexf prod 2 aligned", "fold", "prod", "complexf", 2, 4099, "aligned", ()),
+    ("fold bfloat16 sum 2 aligned", "fold", "sum", "bfloat16", 2, 4099, "aligned", ()),
+    ("fold float max 8 aligned", "fold", "max", "float", 8, 65537, "aligned", ()),
+    ("fold double sum 9 aligned", "fold", "sum", "double", 9, 4099, "aligned", ()),
+    ("fold double sum 2 head", "fold", "sum", "double", 2, 4099, "off8", ()),
+    ("fold short sum 3 shift", "fold", "sum", "short", 3, 4099, "shift", ()),
+    ("fold float sum 2 shift", "fold", "sum", "float", 2, 4099, "shift", ()),
+    ("fold double sum 2 shift", "fold", "sum", "double", 2, 4099, "shift", ()),
+    ("fold complexf prod 2 shift", "fold", "prod", "complexf", 2, 4099, "shift", ()),
+    ("fold bfloat16 max 8 shift", "fold", "max", "bfloat16", 8, 4099, "shift", ()),
+    ("fold bfloat16 sum 9 shift", "fold", "sum", "bfloat16", 9, 4099, "shift", ()),
+    ("fold float sum 3 mixed", "fold", "sum", "float", 3, 4099, "mixed", ()),
+    ("fold longdouble sum 2 elements", "fold", "sum", "longdouble", 2, 1031, "shift", ()),
+    ("fold float sum 2 shift n=1", "fold", "sum", "float", 2, 1, "shift", ()),               # no whole vector
+    ("fold double sum 2 shift n=head", "fold", "sum", "double", 2, 15, "shift", ()),         # 16-byte head
+    ("fold double sum 2 shift n=head+V-1", "fold", "sum", "double", 2, 2, "shift", ()),      # ELEMENTS
+    ("fold double sum 3 n=line head", "fold", "sum", "double", 3, 15, "off8", ()),           # 16-byte head
+    ("fold double sum 3 n=16-byte head", "fold", "sum", "double", 3, 1, "off8", ()),         # ELEMENTS
+    ("orders short sum 2 aligned", "orders", "sum", "short", 2, 4099, "aligned", ()),
+    ("orders float sum 3 aligned", "orders", "sum", "float", 3, 4099, "aligned", ()),
+    ("orders double min 8 aligned", "orders", "min", "double", 8, 4099, "aligned", ()),
+    ("orders longdouble sum 2 aligned", "orders", "sum", "longdouble", 2, 1031, "aligned", ()),
+    ("orders longdouble max 3 aligned", "orders", "max", "longdouble", 3, 1031, "aligned", ()),
+    ("orders complexf prod 2 aligned", "orders", "prod", "complexf", 2, 4099, "aligned", ()),
+    ("orders bfloat16 sum 8 aligned", "orders", "sum", "bfloat16", 8, 4099, "aligned", ()),
+    ("orders float sum 9 aligned", "orders", "sum", "float", 9, 4099, "aligned", ()),
+    ("orders short sum 2 shift", "orders", "sum", "short", 2, 4099, "shift", ()),
+    ("orders float max 3 shift", "orders", "max", "float", 3, 4099, "shift", ()),
+    ("orders double sum 8 shift", "orders", "sum", "double", 8, 65537, "shift", ()),
+    ("orders complexf prod 3 shift", "orders", "prod", "complexf", 3, 4099, "shift", ()),
+    ("orders bfloat16 sum 2 mixed", "orders", "sum", "bfloat16", 2, 4099, "mixed", ()),
+    ("orders longdouble sum 2 elements", "orders", "sum", "longdouble", 2, 1031, "shift", ()),
+    ("orders float sum 3 outputs at two phases", "orders", "sum", "float", 3, 4099, "two", ()),   # ELEMENTS
+    ("orders double sum 3 aligned one null", "orders", "sum", "double", 3, 4099, "aligned", (1,)),
+    ("orders float sum 3 shift one null", "orders", "sum", "float", 3, 4099, "shift", (0,)),
+    ("orders longdouble prod 3 aligned one null", "orders", "prod", "longdouble", 3, 1031, "aligned", (2,)),
+    ("orders double sum 3 n=line head", "orders", "sum", "double", 3, 15, "off8", ()),
+    ("orders double sum 3 n=16-byte head", "orders", "sum", "double", 3, 1, "off8", ()),
+]
+
+# Over the grid cap, so that blocks per CU show: (blocks per CU, vectors per
+# lane) of the launch shape (combine_kernels.h Shape / OrdersShape), the size
+# is cus x blocks x 256 x vectors + 1 vectors; the table holds divmod(grid, cus).
+LAUNCH_CAP_CASES = [
+    ("cap fold float sum 2", "fold", "sum", "float", 2, (4, 1), "aligned", ()),
+    ("cap orders complexf prod 2 aligned", "orders", "prod", "complexf", 2, (2, 1), "aligned", ()),
+    ("cap orders complexf prod 2 shift", "orders", "prod", "complexf", 2, (2, 1), "shift", ()),
+]
+
+
+def _launch_values(op, dtype, nsrc, n, seed):
+    """sources and {member: expected}, bit patterns for bfloat16"""
+    import _half_ref as R
+    import gen_golden
+    if dtype == "bfloat16":
+        srcs = R.sources(dtype, nsrc, n, seed)
+        return srcs, lambda q: R.fold(op, dtype, srcs, q)
+    rng = np.random.default_rng(seed)
+    srcs = [gen_golden.values(rng, op, dtype, n) for _ in range(nsrc)]
+    return srcs, lambda q: oracle.reduce_pe(op, dtype, srcs, q)
+
+
+def _launch_match(shm, ptr, n, want, op, dtype, ctx):
+    if dtype == "bfloat16":
+        got = shm.get(ptr, n, np.uint16)
+        assert (got == want).all(), f"{ctx}: {int((got != want).sum())} of {n} elements differ"
+    else:
+        assert_match(shm.get(ptr, n, dtype), want, op, dtype, ctx=ctx)
+
+
+def _last_launch(shm):
+    import ctypes
+    L = shm.lib
+    L.mi355_last_kernel.restype = ctypes.c_void_p
+    L.mi355_kernel_name.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t]
+    buf = ctypes.create_string_buffer(512)
+    assert L.mi355_kernel_name(L.mi355_last_kernel(), buf, 512) == 0
+    return buf.value.decode(), list(shm.last_launch_grid())
+
+
+def _run_launch_case(shm, dev, case, seed):
+    """One kernel-layer call, its results checked; returns (kernel name, [gx, gy])."""
+    cid, call, op, dtype, nsrc, n, layout, skip = case
+    es = 2 if dtype == "bfloat16" else np.dtype(oracle.NP[dtype]).itemsize
+    if isinstance(n, tuple):
+        n = (shm.device_cus() * n[0] * 256 * n[1] + 1) * (16 // es)
+    if layout == "two":
+        doff, soff, dst_offs = 0, (lambda k: 0), [0, es, 0]
+    else:
+        doff, soff = _launch_layouts(es)[layout]
+        dst_offs = [doff] * nsrc
+    srcs, want = _launch_values(op, dtype, nsrc, n, seed)
+    sp = [_upload_at(dev, x, soff(k)) for k, x in enumerate(srcs)]
+    if call == "fold":
+        out = dev.empty(n * es + 32) + doff
+        assert shm.combine(op, dtype, out, sp, n) == 0
+        launch = _last_launch(shm)
+        shm.sync()
+        _launch_match(shm, out, n, want(0), op, dtype, cid)
+    else:
+        dp = [None if q in skip else dev.empty(n * es + 32) + dst_offs[q] for q in range(nsrc)]
+        assert shm.combine_orders(op, dtype, dp, sp, n) == 0
+        launch = _last_launch(shm)
+        shm.sync()
+        for q in range(nsrc):
+            if dp[q] is not None:
+                _launch_match(shm, dp[q], n, want(q), op, dtype, f"{cid}, member {q}")
+    dev.free()
+    return launch
+
+
+def _nan_word_case(shm, dev):
+    """The NaN words armed, then a call that launches nothing (n = 0), then a
+    fold of NaNs: the first call consumed the request, so the fold neither
+    clears nor sets the word. Returns the fold's launch and the word."""
+    import ctypes
+    L = shm.lib
+    L.mi355_nan_flag_next_launch.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+    L.mi355_nan_flag_next_launch.restype = None
+    n = 4099
+    word = _upload_at(dev, np.array([7], np.uint64), 0)
+    srcs = [np.full(n, np.nan, np.float32), np.arange(n, dtype=np.float32)]
+    sp = [_upload_at(dev, x, 0) for x in srcs]
+    out = dev.empty(n * 4)
+    L.mi355_nan_flag_next_launch(word, word)
+    assert shm.combine("sum", "float", out, sp, 0) == 0
+    assert shm.combine("sum", "float", out, sp, n) == 0
+    launch = _last_launch(shm)
+    shm.sync()
+    assert_match(shm.get(out, n, "float"), oracle.reduce_pe("sum", "float", srcs, 0), "sum", "float", ctx="nan word")
+    seen = int(shm.get(word, 1, np.uint64)[0])
+    dev.free()
+    return launch, seen
+
+
+def launch_identity_records(shm, dev):
+    """{case id: {"kernel": name, "grid": [gx, gy]}}; the cap cases hold
+    "grid_per_cu": divmod(gx, CUs) instead."""
+    rec = {}
+    for i, case in enumerate(LAUNCH_CASES):
+        name, grid = _run_launch_case(shm, dev, case, 8100 + i)
+        rec[case[0]] = {"kernel": name, "grid": grid}
+    cus = shm.device_cus()
+    for i, case in enumerate(LAUNCH_CAP_CASES):
+        name, grid = _run_launch_case(shm, dev, case, 8200 + i)
+        assert grid[1] == 1
+        rec[case[0]] = {"kernel": name, "grid_per_cu": list(divmod(grid[0], cus))}
+    (name, grid), word = _nan_word_case(shm, dev)
+    rec["nan word armed, empty call, fold"] = {"kernel": name, "grid": grid, "word": word}
+    return rec
+
+
+def test_launch_identity_matches_recorded_table(shm, dev):
+    """Every launcher decision that a caller can see -- the kernel
+    instantiation and the grid -- for folds and every-member folds over
+    aligned, shifted and element-wise pointers, 2 to 9 sources (at 9 the last
+    launch), a null output, n at the head, three shapes past the grid cap and
+    a NaN-word request consumed by an empty call: equal to the table recorded
+    from the build that preceded csrc/launch_plan.h, results as the oracle's."""
+    import json
+    import os
+    with open(os.path.join(os.path.dirname(__file__), "golden", "launch_identity.json")) as f:
+        want = json.load(f)
+    got = launch_identity_records(shm, dev)
+    assert sorted(got) == sorted(want)
+    for cid in want:
+        assert got[cid] == want[cid], cid
+    assert want["nan word armed, empty call, fold"]["word"] == 7
