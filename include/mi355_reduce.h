@@ -94,6 +94,24 @@ int mi355_combine (int op, int dtype, void *dst, const void *const *srcs,
 int mi355_combine_orders (int op, int dtype, void *const *dsts, const void *const *srcs,
                           int nsrc, size_t n, void *stream);
 
+/* Every prefix of the left fold at once (the scan collectives' kernel): for
+ * each j < nsrc with dsts[j] != NULL,
+ *   dsts[j][i] = (((srcs[0][i] op srcs[1][i]) op srcs[2][i]) ... op srcs[j][i])
+ * -- mi355_combine of the first j + 1 sources, bit for bit (dsts[0] is a copy
+ * of srcs[0]) -- from one pass over the sources and one running chain: nsrc - 1
+ * operator steps per element. NULL entries are skipped, and the prefixes after
+ * the last non-NULL entry are not computed. dsts[j] may alias srcs[j] exactly
+ * (in place); other overlaps are undefined. Vectors, unaligned source loads
+ * and the element-wise form as for mi355_combine_orders: the outputs must
+ * share one 16-byte phase to run as vectors. 1 <= nsrc <= 32; above 8 sources
+ * the fold runs as chained launches of at most 8, the first source of a launch
+ * being the last output of the one before. Where that output is NULL the
+ * launch leaves it in the last later output that is no source's buffer (that
+ * output's own launch overwrites it); MI355_E_INVAL if there is none, before
+ * anything is launched. Return codes as mi355_combine_orders. */
+int mi355_combine_prefix (int op, int dtype, void *const *dsts, const void *const *srcs,
+                          int nsrc, size_t n, void *stream);
+
 /* nseg independent byte copies dsts[i] <- srcs[i] of nbytes[i] bytes in ONE
  * launch (the all-gather leg of the shard schedule). nseg <= 64. */
 int mi355_copy_segments (void *const *dsts, const void *const *srcs,

@@ -183,7 +183,8 @@ void shmemx_kernel_timing_phase_stats (int phase, long *launches, double *total_
  * by the caller. Returns 0, or -1 before the first call. */
 typedef struct shmemx_call_info {
     char schedule[64];      /* "p2p", "p2p-rounds", "fused-oneshot", "fused-twoshot", "persistent",
-                             * "identity", "exact", "rccl", "staged", "barrier-only" */
+                             * "identity", "exact", "rccl", "staged", "barrier-only"; the scan
+                             * collectives' "scan-*" names are listed with them below */
     char kernel[256];       /* demangled dominant kernel, as rocprofv3 names it ("" for rccl) */
     int ordered;            /* 1: every member's reference order (version areas written) */
     int sources, outputs;   /* buffers the dominant kernel reads / writes */
@@ -453,6 +454,347 @@ void shmemx_bfloat16_max_to_all_on_stream (shmemx_bfloat16_t *target, shmemx_bfl
 void shmemx_bfloat16_min_to_all_on_stream (shmemx_bfloat16_t *target, shmemx_bfloat16_t *source,
         int nreduce, int PE_start, int logPE_stride, int PE_size,
         shmemx_bfloat16_t *pWrk, long *pSync, void *stream);
+
+/* ---- scan collectives: inclusive and exclusive prefix reductions ----
+ * shmemx_<T>_<op>_inscan / _exscan for exactly the (type, op) pairs that have
+ * a *_to_all (the reference's 44 and half/bfloat16 sum, prod, max, min), with
+ * the arguments of that *_to_all. Member j of the active set (its index in
+ * it) receives
+ *   inscan:  src_0 op src_1 op ... op src_j      (member 0: a copy of its source)
+ *   exscan:  src_0 op src_1 op ... op src_(j-1)  (member 0: its target is left
+ *            UNTOUCHED, as MPI_Exscan leaves rank 0's)
+ * as a left fold in ascending member order with the accumulator on the left,
+ * every step the operator *_to_all uses (SSE's NaN rule, libgcc's complex
+ * product, x87 long double; half and bfloat16 rounded to the type at every
+ * step, a NaN out of their sum or prod canonical): member j's inscan is bit
+ * for bit the reference's result on the FIRST member of the set reduced over
+ * members 0 .. j. A scan has one order: shmemx_set_reduce_order does not
+ * apply, and shmemx_set_reduce_algorithm does not change the bits (EXACT and
+ * RCCL requests run the scan schedule; a trace line says so).
+ * As *_to_all: collective and blocking; nreduce == 0 still synchronizes; pWrk
+ * and pSync are never written; target == source is allowed, and partially
+ * overlapping target and source give the result of a call with a copied
+ * source; a one-member set gives inscan = copy, exscan = nothing;
+ * SHMEM_DEBUG=1 exchanges the arguments first. Buffers: the device symmetric
+ * heap, and host objects (staged through the scratch buffers); a device
+ * buffer outside the heap aborts with a message naming the function and the
+ * buffer. shmemx_last_call_info reports "scan-p2p", "scan-p2p-host",
+ * "scan-p2p-rounds", "scan-p2p-host-rounds", "scan-direct", "scan-staged" or
+ * "scan-local". SHMEM_SCAN_DIRECT=1 (a testing aid; set on every PE) forces
+ * the direct schedule of the sets larger than 32 members. There is no
+ * pshmem_ twin, no Fortran wrapper and no stream-ordered form. */
+void shmemx_short_sum_inscan (short *target, short *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        short *pWrk, long *pSync);
+void shmemx_short_prod_inscan (short *target, short *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        short *pWrk, long *pSync);
+void shmemx_short_and_inscan (short *target, short *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        short *pWrk, long *pSync);
+void shmemx_short_or_inscan (short *target, short *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        short *pWrk, long *pSync);
+void shmemx_short_xor_inscan (short *target, short *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        short *pWrk, long *pSync);
+void shmemx_short_max_inscan (short *target, short *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        short *pWrk, long *pSync);
+void shmemx_short_min_inscan (short *target, short *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        short *pWrk, long *pSync);
+void shmemx_int_sum_inscan (int *target, int *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        int *pWrk, long *pSync);
+void shmemx_int_prod_inscan (int *target, int *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        int *pWrk, long *pSync);
+void shmemx_int_and_inscan (int *target, int *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        int *pWrk, long *pSync);
+void shmemx_int_or_inscan (int *target, int *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        int *pWrk, long *pSync);
+void shmemx_int_xor_inscan (int *target, int *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        int *pWrk, long *pSync);
+void shmemx_int_max_inscan (int *target, int *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        int *pWrk, long *pSync);
+void shmemx_int_min_inscan (int *target, int *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        int *pWrk, long *pSync);
+void shmemx_long_sum_inscan (long *target, long *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        long *pWrk, long *pSync);
+void shmemx_long_prod_inscan (long *target, long *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        long *pWrk, long *pSync);
+void shmemx_long_and_inscan (long *target, long *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        long *pWrk, long *pSync);
+void shmemx_long_or_inscan (long *target, long *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        long *pWrk, long *pSync);
+void shmemx_long_xor_inscan (long *target, long *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        long *pWrk, long *pSync);
+void shmemx_long_max_inscan (long *target, long *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        long *pWrk, long *pSync);
+void shmemx_long_min_inscan (long *target, long *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        long *pWrk, long *pSync);
+void shmemx_longlong_sum_inscan (long long *target, long long *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        long long *pWrk, long *pSync);
+void shmemx_longlong_prod_inscan (long long *target, long long *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        long long *pWrk, long *pSync);
+void shmemx_longlong_and_inscan (long long *target, long long *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        long long *pWrk, long *pSync);
+void shmemx_longlong_or_inscan (long long *target, long long *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        long long *pWrk, long *pSync);
+void shmemx_longlong_xor_inscan (long long *target, long long *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        long long *pWrk, long *pSync);
+void shmemx_longlong_max_inscan (long long *target, long long *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        long long *pWrk, long *pSync);
+void shmemx_longlong_min_inscan (long long *target, long long *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        long long *pWrk, long *pSync);
+void shmemx_float_sum_inscan (float *target, float *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        float *pWrk, long *pSync);
+void shmemx_float_prod_inscan (float *target, float *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        float *pWrk, long *pSync);
+void shmemx_float_max_inscan (float *target, float *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        float *pWrk, long *pSync);
+void shmemx_float_min_inscan (float *target, float *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        float *pWrk, long *pSync);
+void shmemx_double_sum_inscan (double *target, double *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        double *pWrk, long *pSync);
+void shmemx_double_prod_inscan (double *target, double *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        double *pWrk, long *pSync);
+void shmemx_double_max_inscan (double *target, double *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        double *pWrk, long *pSync);
+void shmemx_double_min_inscan (double *target, double *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        double *pWrk, long *pSync);
+void shmemx_longdouble_sum_inscan (long double *target, long double *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        long double *pWrk, long *pSync);
+void shmemx_longdouble_prod_inscan (long double *target, long double *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        long double *pWrk, long *pSync);
+void shmemx_longdouble_max_inscan (long double *target, long double *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        long double *pWrk, long *pSync);
+void shmemx_longdouble_min_inscan (long double *target, long double *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        long double *pWrk, long *pSync);
+void shmemx_complexf_sum_inscan (COMPLEXIFY (float) *target, COMPLEXIFY (float) *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        COMPLEXIFY (float) *pWrk, long *pSync);
+void shmemx_complexf_prod_inscan (COMPLEXIFY (float) *target, COMPLEXIFY (float) *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        COMPLEXIFY (float) *pWrk, long *pSync);
+void shmemx_complexd_sum_inscan (COMPLEXIFY (double) *target, COMPLEXIFY (double) *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        COMPLEXIFY (double) *pWrk, long *pSync);
+void shmemx_complexd_prod_inscan (COMPLEXIFY (double) *target, COMPLEXIFY (double) *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        COMPLEXIFY (double) *pWrk, long *pSync);
+void shmemx_half_sum_inscan (shmemx_half_t *target, shmemx_half_t *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        shmemx_half_t *pWrk, long *pSync);
+void shmemx_half_prod_inscan (shmemx_half_t *target, shmemx_half_t *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        shmemx_half_t *pWrk, long *pSync);
+void shmemx_half_max_inscan (shmemx_half_t *target, shmemx_half_t *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        shmemx_half_t *pWrk, long *pSync);
+void shmemx_half_min_inscan (shmemx_half_t *target, shmemx_half_t *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        shmemx_half_t *pWrk, long *pSync);
+void shmemx_bfloat16_sum_inscan (shmemx_bfloat16_t *target, shmemx_bfloat16_t *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        shmemx_bfloat16_t *pWrk, long *pSync);
+void shmemx_bfloat16_prod_inscan (shmemx_bfloat16_t *target, shmemx_bfloat16_t *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        shmemx_bfloat16_t *pWrk, long *pSync);
+void shmemx_bfloat16_max_inscan (shmemx_bfloat16_t *target, shmemx_bfloat16_t *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        shmemx_bfloat16_t *pWrk, long *pSync);
+void shmemx_bfloat16_min_inscan (shmemx_bfloat16_t *target, shmemx_bfloat16_t *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        shmemx_bfloat16_t *pWrk, long *pSync);
+void shmemx_short_sum_exscan (short *target, short *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        short *pWrk, long *pSync);
+void shmemx_short_prod_exscan (short *target, short *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        short *pWrk, long *pSync);
+void shmemx_short_and_exscan (short *target, short *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        short *pWrk, long *pSync);
+void shmemx_short_or_exscan (short *target, short *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        short *pWrk, long *pSync);
+void shmemx_short_xor_exscan (short *target, short *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        short *pWrk, long *pSync);
+void shmemx_short_max_exscan (short *target, short *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        short *pWrk, long *pSync);
+void shmemx_short_min_exscan (short *target, short *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        short *pWrk, long *pSync);
+void shmemx_int_sum_exscan (int *target, int *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        int *pWrk, long *pSync);
+void shmemx_int_prod_exscan (int *target, int *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        int *pWrk, long *pSync);
+void shmemx_int_and_exscan (int *target, int *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        int *pWrk, long *pSync);
+void shmemx_int_or_exscan (int *target, int *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        int *pWrk, long *pSync);
+void shmemx_int_xor_exscan (int *target, int *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        int *pWrk, long *pSync);
+void shmemx_int_max_exscan (int *target, int *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        int *pWrk, long *pSync);
+void shmemx_int_min_exscan (int *target, int *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        int *pWrk, long *pSync);
+void shmemx_long_sum_exscan (long *target, long *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        long *pWrk, long *pSync);
+void shmemx_long_prod_exscan (long *target, long *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        long *pWrk, long *pSync);
+void shmemx_long_and_exscan (long *target, long *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        long *pWrk, long *pSync);
+void shmemx_long_or_exscan (long *target, long *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        long *pWrk, long *pSync);
+void shmemx_long_xor_exscan (long *target, long *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        long *pWrk, long *pSync);
+void shmemx_long_max_exscan (long *target, long *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        long *pWrk, long *pSync);
+void shmemx_long_min_exscan (long *target, long *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        long *pWrk, long *pSync);
+void shmemx_longlong_sum_exscan (long long *target, long long *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        long long *pWrk, long *pSync);
+void shmemx_longlong_prod_exscan (long long *target, long long *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        long long *pWrk, long *pSync);
+void shmemx_longlong_and_exscan (long long *target, long long *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        long long *pWrk, long *pSync);
+void shmemx_longlong_or_exscan (long long *target, long long *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        long long *pWrk, long *pSync);
+void shmemx_longlong_xor_exscan (long long *target, long long *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        long long *pWrk, long *pSync);
+void shmemx_longlong_max_exscan (long long *target, long long *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        long long *pWrk, long *pSync);
+void shmemx_longlong_min_exscan (long long *target, long long *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        long long *pWrk, long *pSync);
+void shmemx_float_sum_exscan (float *target, float *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        float *pWrk, long *pSync);
+void shmemx_float_prod_exscan (float *target, float *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        float *pWrk, long *pSync);
+void shmemx_float_max_exscan (float *target, float *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        float *pWrk, long *pSync);
+void shmemx_float_min_exscan (float *target, float *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        float *pWrk, long *pSync);
+void shmemx_double_sum_exscan (double *target, double *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        double *pWrk, long *pSync);
+void shmemx_double_prod_exscan (double *target, double *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        double *pWrk, long *pSync);
+void shmemx_double_max_exscan (double *target, double *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        double *pWrk, long *pSync);
+void shmemx_double_min_exscan (double *target, double *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        double *pWrk, long *pSync);
+void shmemx_longdouble_sum_exscan (long double *target, long double *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        long double *pWrk, long *pSync);
+void shmemx_longdouble_prod_exscan (long double *target, long double *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        long double *pWrk, long *pSync);
+void shmemx_longdouble_max_exscan (long double *target, long double *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        long double *pWrk, long *pSync);
+void shmemx_longdouble_min_exscan (long double *target, long double *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        long double *pWrk, long *pSync);
+void shmemx_complexf_sum_exscan (COMPLEXIFY (float) *target, COMPLEXIFY (float) *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        COMPLEXIFY (float) *pWrk, long *pSync);
+void shmemx_complexf_prod_exscan (COMPLEXIFY (float) *target, COMPLEXIFY (float) *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        COMPLEXIFY (float) *pWrk, long *pSync);
+void shmemx_complexd_sum_exscan (COMPLEXIFY (double) *target, COMPLEXIFY (double) *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        COMPLEXIFY (double) *pWrk, long *pSync);
+void shmemx_complexd_prod_exscan (COMPLEXIFY (double) *target, COMPLEXIFY (double) *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        COMPLEXIFY (double) *pWrk, long *pSync);
+void shmemx_half_sum_exscan (shmemx_half_t *target, shmemx_half_t *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        shmemx_half_t *pWrk, long *pSync);
+void shmemx_half_prod_exscan (shmemx_half_t *target, shmemx_half_t *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        shmemx_half_t *pWrk, long *pSync);
+void shmemx_half_max_exscan (shmemx_half_t *target, shmemx_half_t *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        shmemx_half_t *pWrk, long *pSync);
+void shmemx_half_min_exscan (shmemx_half_t *target, shmemx_half_t *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        shmemx_half_t *pWrk, long *pSync);
+void shmemx_bfloat16_sum_exscan (shmemx_bfloat16_t *target, shmemx_bfloat16_t *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        shmemx_bfloat16_t *pWrk, long *pSync);
+void shmemx_bfloat16_prod_exscan (shmemx_bfloat16_t *target, shmemx_bfloat16_t *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        shmemx_bfloat16_t *pWrk, long *pSync);
+void shmemx_bfloat16_max_exscan (shmemx_bfloat16_t *target, shmemx_bfloat16_t *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        shmemx_bfloat16_t *pWrk, long *pSync);
+void shmemx_bfloat16_min_exscan (shmemx_bfloat16_t *target, shmemx_bfloat16_t *source,
+        int nreduce, int PE_start, int logPE_stride, int PE_size,
+        shmemx_bfloat16_t *pWrk, long *pSync);
 
 #ifdef __cplusplus
 }

@@ -1636,3 +1636,398 @@ MINMAX (longdouble, long double, MI355_LONGDOUBLE)
 
 SHMEMX_REDUCE_TYPE (half, MI355_HALF)
 SHMEMX_REDUCE_TYPE (bfloat16, MI355_BFLOAT16)
+
+/* ---------------------------------------------------------------------- */
+/* scan: shmemx_<T>_<op>_inscan / _exscan (shmemx.h)                       */
+/* ---------------------------------------------------------------------- */
+/* Member j of the active set receives the left fold of the sources of
+ * members 0 .. j (inscan) or 0 .. j - 1 (exscan; member 0's target is left
+ * untouched), in ascending member order with the accumulator on the left.
+ * There is one order, so the result-order setting does not apply, and the
+ * algorithm setting does not change the bits: every request runs one of
+ *
+ *   shard    (up to MI355_ORDERS_MAX_SOURCES members) the every-member-order
+ *            schedule with another kernel: barrier; the owner of shard i
+ *            reads every member's source shard once and writes EVERY prefix
+ *            of it (mi355_combine_prefix) -- its own into its target shard,
+ *            member q's into slot q of its version area; barrier; every
+ *            member gathers its version of the other shards
+ *            (gather_segments, unchanged); barrier. Device-flag or host
+ *            barriers, and several rounds when the versions outgrow the
+ *            version area, as p2p_any.
+ *   direct   (larger sets, or SHMEM_SCAN_DIRECT=1, a testing aid) between two
+ *            host barriers member j folds the whole arrays of members 0 .. j
+ *            with mi355_combine: j + 1 times the reads instead of one.
+ *
+ * The kernels take an output that aliases the source of its own slot only
+ * (mi355_reduce.h). In place that is inscan's shard fold; exscan in place
+ * (the owner's prefix me - 1 would land on source me), the direct schedule
+ * in place (the target would be the fold's last source) and partially
+ * overlapping buffers go through scratch buffer C, as reduce_symmetric's
+ * overlapping calls do. */
+#include "prefix_plan.h"
+
+static int scan_direct_forced (void)
+{
+    static int forced = -1;
+    if (forced < 0) {
+        const char *e = getenv ("SHMEM_SCAN_DIRECT");
+        forced = e != NULL && atoi (e) != 0;
+    }
+    return forced;
+}
+
+static int scan_is_direct (const struct aset *s)
+{
+    return s->size > MI355_ORDERS_MAX_SOURCES || scan_direct_forced ();
+}
+
+/* The owner's leg: every prefix of this PE's shard. 0: queued, or nothing
+ * to do (an empty shard). */
+static int scan_fold_shard (int op, int dtype, size_t es, size_t dst_off, size_t src_off, size_t n,
+                            const struct aset *s, int excl, int chan, hipStream_t st)
+{
+    const void *sp[MI355_ORDERS_MAX_SOURCES];
+    void *dsts[MI355_ORDERS_MAX_SOURCES];
+    size_t lo, hi;
+    mi355_shard_bounds (n, es, s->size, s->me, &lo, &hi);
+    if (hi <= lo)
+        return 0;
+    const int nsrc = mi355_scan_sources (excl, s->size);
+    const size_t slot = ver_slot_bytes (n, es, s->size);
+    for (int q = 0; q < nsrc; ++q) {
+        sp[q] = shmemi_peer_ptr (aset_pe (s, q), src_off + lo * es);
+        dsts[q] = NULL;
+    }
+    for (int q = 0; q < s->size; ++q) {
+        const int j = mi355_scan_slot (excl, q);
+        if (j < 0)
+            continue; /* exscan's member 0 receives nothing */
+        dsts[j] = q == s->me ? shmemi_peer_ptr (shmemi.mype, dst_off + lo * es)
+                             : shmemi_peer_ptr (shmemi.mype, ver_off (chan, s->me, q, slot, dst_off));
+    }
+    const int rc = mi355_combine_prefix (op, dtype, dsts, sp, nsrc, hi - lo, st);
+    if (rc == 0)
+        note_call (1, nsrc, nsrc, nsrc - (s->me < nsrc ? 1 : 0), (unsigned long long) ((hi - lo) * es), 0, 0,
+                   mi355_last_kernel ());
+    return rc;
+}
+
+/* exscan's member 0 gathers nothing: its target stays as it was */
+static int scan_gather (size_t es, size_t dst_off, size_t n, const struct aset *s, int excl, int chan, void **dsts,
+                        const void **sp, size_t *nb)
+{
+    if (excl && s->me == 0)
+        return 0;
+    return gather_segments (es, dst_off, n, s, 1, chan, dsts, sp, nb);
+}
+
+/* The shard schedule with device-flag barriers (p2p_range_dev's shape) */
+static void scan_range_dev (int op, int dtype, size_t es, size_t dst_off, size_t src_off, size_t n,
+                            const struct aset *s, int excl)
+{
+    MI355FusedArgs a;
+    member_args (&a, s, SHMEMI_CHAN_HOST);
+    void *dsts[MI355_FUSED_MAX_MEMBERS];
+    const void *sp[MI355_FUSED_MAX_MEMBERS];
+    size_t nb[MI355_FUSED_MAX_MEMBERS];
+
+    device_barrier (&a, shmemi.stream); /* every source is ready */
+    shmemi_peer_acquire (shmemi.stream);
+    shmemi_timed_begin ();
+    int rc = scan_fold_shard (op, dtype, es, dst_off, src_off, n, s, excl, SHMEMI_CHAN_HOST, shmemi.stream);
+    shmemi_timed_end ();
+    if (rc != 0)
+        shmemi_fatal ("prefix kernel launch failed (op %d, dtype %d, %d members, %zu elements): %d", op, dtype,
+                      s->size, n, rc);
+    device_barrier (&a, shmemi.stream); /* every shard's prefixes are written */
+    shmemi_peer_acquire (shmemi.stream);
+    const int k = scan_gather (es, dst_off, n, s, excl, SHMEMI_CHAN_HOST, dsts, sp, nb);
+    if (k > 0) {
+        shmemi_timed_begin_phase (1);
+        rc = mi355_copy_segments (dsts, sp, nb, k, shmemi.stream);
+        shmemi_timed_end ();
+        if (rc != 0)
+            shmemi_fatal ("copy kernel launch failed: %d", rc);
+    }
+    a.host_flag = shmemi.sig_flag; /* peers are done reading us: the call is over */
+    a.epoch = shmemi_next_epoch ();
+    device_barrier (&a, shmemi.stream);
+    if (shmemi_wait_flag (a.epoch) != a.epoch)
+        shmemi_fatal ("device barrier timed out waiting for the other PEs of the active set");
+}
+
+/* The shard schedule with host barriers (p2p_range's shape) */
+static void scan_range (int op, int dtype, size_t es, size_t dst_off, size_t src_off, size_t n,
+                        const struct aset *s, int excl)
+{
+    const void **sp = (const void **) malloc (sizeof (void *) * (size_t) s->size);
+    void **dsts = (void **) malloc (sizeof (void *) * (size_t) s->size);
+    size_t *nb = (size_t *) malloc (sizeof (size_t) * (size_t) s->size);
+    if (sp == NULL || dsts == NULL || nb == NULL)
+        shmemi_fatal ("out of host memory");
+    size_t lo, hi;
+    mi355_shard_bounds (n, es, s->size, s->me, &lo, &hi);
+
+    host_order ();
+    shmemi_barrier_set (s->start, s->stride, s->size); /* every source is ready */
+    if (hi > lo) {
+        shmemi_peer_acquire (shmemi.stream);
+        shmemi_timed_begin ();
+        shmemi_arm_signal ();
+        const int rc = scan_fold_shard (op, dtype, es, dst_off, src_off, n, s, excl, SHMEMI_CHAN_HOST, shmemi.stream);
+        shmemi_timed_end ();
+        if (rc != 0)
+            shmemi_fatal ("prefix kernel launch failed (op %d, dtype %d, %d members, %zu elements): %d", op, dtype,
+                          s->size, n, rc);
+        shmemi_wait_signal ();
+    }
+    shmemi_barrier_set (s->start, s->stride, s->size); /* every shard's prefixes are written */
+    shmemi_peer_acquire (shmemi.stream);
+    const int k = scan_gather (es, dst_off, n, s, excl, SHMEMI_CHAN_HOST, dsts, sp, nb);
+    copy_wait (dsts, sp, nb, k, 1);
+    shmemi_barrier_set (s->start, s->stride, s->size); /* peers are done reading us */
+    free (nb);
+    free (dsts);
+    free (sp);
+}
+
+/* The direct schedule: this member's fold of the whole arrays; dst must not
+ * overlap any source (scan_symmetric routes overlaps through scratch). */
+static void scan_direct (int op, int dtype, size_t es, size_t dst_off, size_t src_off, size_t n, const struct aset *s,
+                         int excl)
+{
+    const int k = mi355_scan_slot (excl, s->me) + 1; /* sources 0 .. k - 1 */
+    host_order ();
+    shmemi_barrier_set (s->start, s->stride, s->size); /* every source is ready */
+    if (k > 0) {
+        const void **sp = (const void **) malloc (sizeof (void *) * (size_t) k);
+        if (sp == NULL)
+            shmemi_fatal ("out of host memory");
+        shmemi_peer_acquire (shmemi.stream);
+        for (int i = 0; i < k; ++i)
+            sp[i] = shmemi_peer_ptr (aset_pe (s, i), src_off);
+        combine_wait (op, dtype, shmemi_peer_ptr (shmemi.mype, dst_off), sp, k, n, 1);
+        note_call (1, k, 1, k - (s->me < k ? 1 : 0), (unsigned long long) (n * es), 0, 0, mi355_last_kernel ());
+        free (sp);
+    }
+    shmemi_barrier_set (s->start, s->stride, s->size); /* peers are done reading us */
+}
+
+/* One scan of [0, n) at symmetric offsets, dst and src disjoint (or, shard
+ * schedule of an inscan, identical); ends with a barrier of the set. */
+static void scan_any (int op, int dtype, size_t es, size_t dst_off, size_t src_off, size_t n, const struct aset *s,
+                      int excl)
+{
+    if (scan_is_direct (s)) {
+        SHMEMI_TRACE (SHMEMI_LOG_REDUCTION, "schedule: scan, direct: each member folds its prefix of the whole "
+                                            "arrays, host barriers (%zu elements, %d members)", n, s->size);
+        begin_call ("scan-direct");
+        scan_direct (op, dtype, es, dst_off, src_off, n, s, excl);
+        return;
+    }
+    const int dev = device_flags_ok (s);
+    const size_t round = ordered_round_elems (es, s->size);
+    SHMEMI_TRACE (SHMEMI_LOG_REDUCTION, "schedule: scan, P2P shards, %s barriers, every prefix from one pass "
+                                        "(%zu elements, %d members%s)", dev ? "device" : "host", n, s->size,
+                  n > round ? ", several rounds" : "");
+    begin_call (dev ? (n > round ? "scan-p2p-rounds" : "scan-p2p") : (n > round ? "scan-p2p-host-rounds" : "scan-p2p-host"));
+    size_t b = 0;
+    do {
+        const size_t cn = n - b < round ? n - b : round;
+        if (dev)
+            scan_range_dev (op, dtype, es, dst_off + b * es, src_off + b * es, cn, s, excl);
+        else
+            scan_range (op, dtype, es, dst_off + b * es, src_off + b * es, cn, s, excl);
+        b += cn;
+    } while (b < n);
+}
+
+static void scan_symmetric (int op, int dtype, size_t es, size_t dst_off, size_t src_off, size_t n,
+                            const struct aset *s, int excl)
+{
+    const size_t nbytes = n * es;
+    const int same = dst_off == src_off;
+    const int overlap = ranges_overlap (dst_off, src_off, nbytes);
+    const int receives = !(excl && s->me == 0); /* this member's target is written */
+    if (s->size > 1 && shmemi.p2p_broken)
+        shmemi_fatal ("peer GPU memory reads failed the init self-test; the scan collectives need them");
+    if (s->size > 1 && (shmemi.algorithm == SHMEMX_REDUCE_EXACT || shmemi.algorithm == SHMEMX_REDUCE_RCCL))
+        SHMEMI_TRACE (SHMEMI_LOG_REDUCTION, "scan: the %s request does not apply (a scan has one order and RCCL has "
+                                            "no scan); running the scan schedule",
+                      shmemi.algorithm == SHMEMX_REDUCE_EXACT ? "EXACT" : "RCCL");
+    if (s->size == 1) {
+        SHMEMI_TRACE (SHMEMI_LOG_REDUCTION, "schedule: scan of one member: %s",
+                      excl ? "exscan, nothing to do" : same ? "inscan in place, nothing to move" : "inscan, one copy");
+        begin_call ("scan-local");
+        if (excl || same)
+            return;
+        if (!overlap) {
+            copy_local (dst_off, src_off, nbytes, 1);
+            return;
+        }
+    } else if (!overlap || (same && !excl && !scan_is_direct (s))) {
+        scan_any (op, dtype, es, dst_off, src_off, n, s, excl);
+        return;
+    }
+
+    /* through scratch buffer C, chunk by chunk, walking down when target
+     * lies above source (memmove order), as reduce_symmetric */
+    const size_t tmp_off = shmemi.scratch_off + 2 * shmemi.scratch_chunk;
+    const size_t per = shmemi.scratch_chunk / es;
+    const size_t nchunks = (n + per - 1) / per;
+    const int down = dst_off > src_off;
+    SHMEMI_TRACE (SHMEMI_LOG_REDUCTION, "schedule: scan with overlapping target, %zu chunk(s) through scratch, %s",
+                  nchunks, down ? "top down" : "bottom up");
+    for (size_t c = 0; c < nchunks; ++c) {
+        const size_t idx = down ? nchunks - 1 - c : c;
+        const size_t b = idx * per;
+        const size_t cn = n - b < per ? n - b : per;
+        if (s->size == 1)
+            copy_local (tmp_off, src_off + b * es, cn * es, 0);
+        else
+            scan_any (op, dtype, es, tmp_off, src_off + b * es, cn, s, excl);
+        if (receives)
+            copy_local (dst_off + b * es, tmp_off, cn * es, 0);
+    }
+    if (s->size > 1)
+        shmemi_barrier_set (s->start, s->stride, s->size);
+}
+
+/* Host-heap (shmem_malloc) and other host arrays: each chunk goes into
+ * scratch A, is scanned into scratch B and comes back out, in memmove order
+ * when target and source overlap. Blocking copies: no double buffering. */
+static void scan_staged (int op, int dtype, void *target, const void *source, size_t n, const struct aset *s,
+                         int excl)
+{
+    const size_t es = mi355_dtype_size (dtype);
+    const size_t per = shmemi.scratch_chunk / es;
+    const size_t nchunks = (n + per - 1) / per;
+    const size_t a_off = shmemi.scratch_off, b_off = shmemi.scratch_off + shmemi.scratch_chunk;
+    const int receives = !(excl && s->me == 0);
+    const int down = (const char *) target > (const char *) source &&
+                     (const char *) target < (const char *) source + n * es;
+    for (size_t c = 0; c < nchunks; ++c) {
+        const size_t idx = down ? nchunks - 1 - c : c;
+        const size_t b = idx * per;
+        const size_t cn = n - b < per ? n - b : per;
+        SHMEMI_HIP (hipMemcpy (shmemi.heap + a_off, (const char *) source + b * es, cn * es, hipMemcpyDefault));
+        scan_symmetric (op, dtype, es, b_off, a_off, cn, s, excl);
+        if (receives)
+            SHMEMI_HIP (hipMemcpy ((char *) target + b * es, shmemi.heap + b_off, cn * es, hipMemcpyDefault));
+    }
+}
+
+static void scan_impl (int op, int dtype, int excl, const char *fn, void *target, const void *source, int nreduce,
+                       int PE_start, int logPE_stride, int PE_size, long *pSync)
+{
+    shmemi_init_check (fn);
+    if (logPE_stride < 0 || logPE_stride > 30 || PE_size < 1 || PE_start < 0 ||
+        PE_start + (long) (PE_size - 1) * (1L << logPE_stride) >= shmemi.npes)
+        shmemi_fatal ("%s: active set (PE_start %d, logPE_stride %d, PE_size %d) outside the %d PEs", fn, PE_start,
+                      logPE_stride, PE_size, shmemi.npes);
+    struct aset s = {PE_start, 1 << logPE_stride, PE_size, -1};
+    for (int i = 0; i < PE_size; ++i)
+        if (aset_pe (&s, i) == shmemi.mype)
+            s.me = i;
+    if (s.me < 0)
+        shmemi_fatal ("%s: PE %d is not in the active set (PE_start %d, logPE_stride %d, PE_size %d)", fn,
+                      shmemi.mype, PE_start, logPE_stride, PE_size);
+    if (nreduce < 0)
+        shmemi_fatal ("%s: nreduce %d < 0", fn, nreduce);
+    if (shmemi.debug && pSync != NULL && (pSync[0] != SHMEM_SYNC_VALUE || pSync[1] != SHMEM_SYNC_VALUE))
+        shmemi_fatal ("%s: pSync not initialised to SHMEM_SYNC_VALUE", fn);
+
+    const size_t es = mi355_dtype_size (dtype);
+    const size_t n = (size_t) nreduce;
+    if (shmemi.debug)
+        debug_check (fn, op, dtype, target, source, nreduce, PE_start, logPE_stride, PE_size);
+    if (n == 0) {
+        begin_call ("barrier-only");
+        shmemi_barrier_set (s.start, s.stride, s.size);
+        shmemi_barrier_set (s.start, s.stride, s.size);
+        return;
+    }
+    if (shmemi.heap == NULL)
+        shmemi_fatal ("%s: no GPU: this library reduces on the GPU only (SHMEM_BOOTSTRAP_ONLY set?)", fn);
+    if (target == NULL || source == NULL)
+        shmemi_fatal ("%s: NULL target or source", fn);
+    const size_t nbytes = n * es;
+    const int kt = ptr_kind (target, nbytes), ks = ptr_kind (source, nbytes);
+    if (kt == PK_DEV_OTHER || ks == PK_DEV_OTHER)
+        shmemi_fatal ("%s: %s is device memory outside the symmetric heap; the scan collectives take device-heap "
+                      "(shmemx_malloc_device) and host objects only", fn, kt == PK_DEV_OTHER ? "target" : "source");
+    if (kt != PK_HOST || ks != PK_HOST)
+        shmemi_order_after_caller (0); /* SHMEM_ENTRY_SYNC */
+    caller_order_pending = s.size > 1 && kt == PK_DEV_SYM && ks == PK_DEV_SYM;
+    if (shmemi_trace_mask & (1u << SHMEMI_LOG_REDUCTION)) {
+        static const char *const kind[] = {"host", "device heap", "device, not symmetric"};
+        const int overlap = target != source && ranges_overlap ((size_t) target, (size_t) source, nbytes);
+        SHMEMI_TRACE (SHMEMI_LOG_REDUCTION,
+                      "%s: nreduce %d, PE_start %d, logPE_stride %d, PE_size %d; target %p (%s), source %p (%s)", fn,
+                      nreduce, PE_start, logPE_stride, PE_size, target, kind[kt], source, kind[ks]);
+        SHMEMI_TRACE (SHMEMI_LOG_REDUCTION, "target (%p) and source (%p, size %zu) %s", target, source, nbytes,
+                      target == source ? "are the same buffer" : overlap ? "overlap, using temporary target"
+                                                                          : "do not overlap");
+    }
+    if (kt == PK_DEV_SYM && ks == PK_DEV_SYM) {
+        scan_symmetric (op, dtype, es, shmemi_heap_offset (target), shmemi_heap_offset (source), n, &s, excl);
+        return;
+    }
+    SHMEMI_TRACE (SHMEMI_LOG_REDUCTION, "scan staged through the scratch buffers");
+    begin_call ("scan-staged");
+    scan_staged (op, dtype, target, source, n, &s, excl);
+    shmemi.last.schedule = "scan-staged"; /* the kernel fields: the last chunk's scan */
+}
+
+/* the 52 (type, op) pairs of *_to_all, each as inscan and exscan: shmemx_ names only */
+#define SHMEMX_SCAN(Name, Op, Type, DT, OPC)                                                              \
+    void shmemx_##Name##_##Op##_inscan (Type *target, Type *source, int nreduce, int PE_start,            \
+                                        int logPE_stride, int PE_size, Type *pWrk, long *pSync)           \
+    {                                                                                                     \
+        (void) pWrk;                                                                                      \
+        scan_impl (OPC, DT, 0, "shmemx_" #Name "_" #Op "_inscan", target, source, nreduce, PE_start,     \
+                   logPE_stride, PE_size, pSync);                                                         \
+    }                                                                                                     \
+    void shmemx_##Name##_##Op##_exscan (Type *target, Type *source, int nreduce, int PE_start,            \
+                                        int logPE_stride, int PE_size, Type *pWrk, long *pSync)           \
+    {                                                                                                     \
+        (void) pWrk;                                                                                      \
+        scan_impl (OPC, DT, 1, "shmemx_" #Name "_" #Op "_exscan", target, source, nreduce, PE_start,     \
+                   logPE_stride, PE_size, pSync);                                                         \
+    }
+#define SCAN_SUMPROD(Name, Type, DT)                   \
+    SHMEMX_SCAN (Name, sum, Type, DT, MI355_OP_SUM)    \
+    SHMEMX_SCAN (Name, prod, Type, DT, MI355_OP_PROD)
+#define SCAN_LOGIC(Name, Type, DT)                     \
+    SHMEMX_SCAN (Name, and, Type, DT, MI355_OP_AND)    \
+    SHMEMX_SCAN (Name, or, Type, DT, MI355_OP_OR)      \
+    SHMEMX_SCAN (Name, xor, Type, DT, MI355_OP_XOR)
+#define SCAN_MINMAX(Name, Type, DT)                    \
+    SHMEMX_SCAN (Name, max, Type, DT, MI355_OP_MAX)    \
+    SHMEMX_SCAN (Name, min, Type, DT, MI355_OP_MIN)
+
+SCAN_SUMPROD (short, short, MI355_SHORT)
+SCAN_SUMPROD (int, int, MI355_INT)
+SCAN_SUMPROD (long, long, MI355_LONG)
+SCAN_SUMPROD (longlong, long long, MI355_LONGLONG)
+SCAN_SUMPROD (double, double, MI355_DOUBLE)
+SCAN_SUMPROD (float, float, MI355_FLOAT)
+SCAN_SUMPROD (longdouble, long double, MI355_LONGDOUBLE)
+SCAN_SUMPROD (complexd, double _Complex, MI355_COMPLEXD)
+SCAN_SUMPROD (complexf, float _Complex, MI355_COMPLEXF)
+SCAN_SUMPROD (half, shmemx_half_t, MI355_HALF)
+SCAN_SUMPROD (bfloat16, shmemx_bfloat16_t, MI355_BFLOAT16)
+SCAN_LOGIC (short, short, MI355_SHORT)
+SCAN_LOGIC (int, int, MI355_INT)
+SCAN_LOGIC (long, long, MI355_LONG)
+SCAN_LOGIC (longlong, long long, MI355_LONGLONG)
+SCAN_MINMAX (short, short, MI355_SHORT)
+SCAN_MINMAX (int, int, MI355_INT)
+SCAN_MINMAX (long, long, MI355_LONG)
+SCAN_MINMAX (longlong, long long, MI355_LONGLONG)
+SCAN_MINMAX (double, double, MI355_DOUBLE)
+SCAN_MINMAX (float, float, MI355_FLOAT)
+SCAN_MINMAX (longdouble, long double, MI355_LONGDOUBLE)
+SCAN_MINMAX (half, shmemx_half_t, MI355_HALF)
+SCAN_MINMAX (bfloat16, shmemx_bfloat16_t, MI355_BFLOAT16)

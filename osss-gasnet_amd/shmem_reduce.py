@@ -103,6 +103,7 @@ def load(path=LIB_PATH):
         "mi355_dtype_size": ([_i], _sz), "mi355_op_supported": ([_i, _i], _i),
         "mi355_combine": ([_i, _i, _vp, ctypes.POINTER(_vp), _i, _sz, _vp], _i),
         "mi355_combine_orders": ([_i, _i, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _i, _sz, _vp], _i),
+        "mi355_combine_prefix": ([_i, _i, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _i, _sz, _vp], _i),
         "mi355_copy_segments": ([ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_sz), _i, _vp], _i),
         "mi355_copy_direction_next_launch": ([_i], None),
         "mi355_device_cus": ([], _i),
@@ -266,6 +267,44 @@ class Shmem:
         if dtype is None:
             raise TypeError(f"no shmem_*_to_all for {source.dtype}")
         self.to_all(op, dtype, target.data_ptr(), source.data_ptr(), source.numel(), PE_start, logPE_stride, PE_size)
+
+    # ---- scan: inclusive / exclusive prefix reductions (include/shmemx.h)
+    def _scan_fn(self, op, dtype, exclusive):
+        key = ("scan", op, dtype, bool(exclusive))
+        f = self._fns.get(key)
+        if f is None:
+            f = getattr(self.lib, f"shmemx_{dtype}_{op}_{'exscan' if exclusive else 'inscan'}")
+            f.restype = None
+            f.argtypes = [_vp, _vp, _i, _i, _i, _i, _vp, _vp]
+            self._fns[key] = f
+        return f
+
+    def scan(self, op, dtype, target, source, nreduce, PE_start=0, logPE_stride=0, PE_size=None, exclusive=False,
+             pWrk=None, pSync=None):
+        """shmemx_<T>_<op>_inscan (exclusive: _exscan): member j of the active
+        set receives src_0 op ... op src_j (exclusive: ... op src_(j-1), and
+        member 0's target is left untouched). Blocking."""
+        if PE_size is None:
+            PE_size = self.n_pes()
+        if pSync is None:
+            pSync = self._psync_ptr
+        self._scan_fn(op, dtype, exclusive)(target, source, nreduce, PE_start, logPE_stride, PE_size, pWrk, pSync)
+
+    def scan_tensors(self, op, out, x, PE_start=0, logPE_stride=0, PE_size=None, exclusive=False):
+        """scan() on two contiguous tensors of one dtype from heap_tensor (the
+        scan collectives take device buffers of the symmetric heap only); every
+        torch dtype to_all_tensors maps, float16 and bfloat16 included."""
+        if out.dtype != x.dtype or out.numel() != x.numel():
+            raise ValueError("out and x must have the same dtype and number of elements")
+        if not (out.is_contiguous() and x.is_contiguous()) or out.device.type != "cuda" or x.device.type != "cuda":
+            raise ValueError("out and x must be contiguous GPU tensors")
+        dtype = TORCH_DTYPES.get(str(x.dtype).replace("torch.", ""))
+        if dtype is None:
+            raise TypeError(f"no scan for {x.dtype}")
+        for t in (out, x):
+            if t.numel() and not self.lib.shmemx_is_device_symmetric(t.data_ptr()):
+                raise ValueError("scan_tensors takes tensors from heap_tensor (the device symmetric heap)")
+        self.scan(op, dtype, out.data_ptr(), x.data_ptr(), x.numel(), PE_start, logPE_stride, PE_size, exclusive)
 
     # ---- all-to-all (include/shmem.h)
     def _alltoall_fn(self, bits, strided):
@@ -459,6 +498,12 @@ class Shmem:
         d = (_vp * len(dsts))(*[x if x else None for x in dsts])
         s = (_vp * len(srcs))(*srcs)
         return self.lib.mi355_combine_orders(OPS.index(op), DTYPES.index(dtype), d, s, len(srcs), n, stream)
+
+    def combine_prefix(self, op, dtype, dsts, srcs, n, stream=None):
+        """dsts[j] (or None) <- srcs[0] op ... op srcs[j], every prefix from one pass (mi355_combine_prefix)"""
+        d = (_vp * len(dsts))(*[x if x else None for x in dsts])
+        s = (_vp * len(srcs))(*srcs)
+        return self.lib.mi355_combine_prefix(OPS.index(op), DTYPES.index(dtype), d, s, len(srcs), n, stream)
 
     def device_cus(self):
         """mi355_device_cus: the CU count the launchers cap their grids with"""
