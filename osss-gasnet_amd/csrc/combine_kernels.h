@@ -823,6 +823,28 @@ int launch_fixed(void *dst, const void *const *srcs, size_t n, hipStream_t st, b
     return launch(k, dim3(grid_for((uint64_t)kBlock * S::unroll, p.nvec, bpc)), st, p, final);
 }
 
+// The vector launch's grid of the every-member fold and of the prefix fold
+// (prefix_kernels.h), which both run OrdersShape<OP, NSRC, T>; k: the kernel.
+template <int OP, typename T, int NSRC>
+static unsigned orders_grid(const void *k, PlanKind plan_kind, uint64_t nvec) {
+    using S = OrdersShape<OP, NSRC, T>;
+    // the residency cap: ALU-heavy shapes only (long double, which never takes SHIFT)
+    int bpc = S::blocks_per_cu;
+    if (S::alu_heavy && resident_blocks(k) < bpc) bpc = resident_blocks(k);
+    // the measured ALU-heavy folds -- x87 sum/product, float complex
+    // product (profiles/r04/alu_grid/) -- one vector per lane, every
+    // block queued at once, so the hardware hands out the last round's
+    // work as slots free instead of a resident grid's fixed rounds.
+    // ALIGNED only: the float complex product's SHIFT launch has always kept
+    // S::blocks_per_cu. That may be an oversight of the shifted kernels'
+    // introduction; it stays until a measurement says otherwise (a tuning
+    // change, not a refactoring).
+    if (plan_kind == PLAN_ALIGNED && ((S::alu_heavy && (OP == MI355_OP_SUM || OP == MI355_OP_PROD)) ||
+                                      (std::is_same<T, cplxf>::value && OP == MI355_OP_PROD)))
+        bpc = 1 << 20;
+    return grid_for((uint64_t)kBlock * S::unroll, nvec, bpc);
+}
+
 // mi355_combine_orders for NSRC <= kMaxSrc sources: one launch
 template <int OP, typename T, int NSRC>
 int launch_orders_fixed(void *const *dsts, const void *const *srcs, size_t n, hipStream_t st) {
@@ -848,21 +870,7 @@ int launch_orders_fixed(void *const *dsts, const void *const *srcs, size_t n, hi
     }
     if (plan.kind == PLAN_ELEMENTS)
         return launch(combine_orders_scalar<OP, T, NSRC>, dim3(grid_for((uint64_t)kBlock * 4, n)), st, p);
-    // the residency cap: ALU-heavy shapes only (long double, which never takes SHIFT)
-    int bpc = S::blocks_per_cu;
-    if (S::alu_heavy && resident_blocks((const void *)k) < bpc) bpc = resident_blocks((const void *)k);
-    // the measured ALU-heavy folds -- x87 sum/product, float complex
-    // product (profiles/r04/alu_grid/) -- one vector per lane, every
-    // block queued at once, so the hardware hands out the last round's
-    // work as slots free instead of a resident grid's fixed rounds.
-    // ALIGNED only: the float complex product's SHIFT launch has always kept
-    // S::blocks_per_cu. That may be an oversight of the shifted kernels'
-    // introduction; it stays until a measurement says otherwise (a tuning
-    // change, not a refactoring).
-    if (plan.kind == PLAN_ALIGNED && ((S::alu_heavy && (OP == MI355_OP_SUM || OP == MI355_OP_PROD)) ||
-                                      (std::is_same<T, cplxf>::value && OP == MI355_OP_PROD)))
-        bpc = 1 << 20;
-    return launch(k, dim3(grid_for((uint64_t)kBlock * S::unroll, p.nvec, bpc)), st, p);
+    return launch(k, dim3(orders_grid<OP, T, NSRC>((const void *)k, plan.kind, p.nvec)), st, p);
 }
 
 template <int OP, typename T>

@@ -150,14 +150,7 @@ int launch_prefix_fixed(void *const *dsts, const void *const *srcs, size_t n, hi
     if constexpr (shiftable) {
         if (plan.kind == PLAN_SHIFT) k = combine_prefix_vec<OP, T, NSRC, S::unroll, S::policy, true>;
     }
-    // the residency cap and the uncapped grids of the ALU-heavy folds, as
-    // launch_orders_fixed
-    int bpc = S::blocks_per_cu;
-    if (S::alu_heavy && resident_blocks((const void *)k) < bpc) bpc = resident_blocks((const void *)k);
-    if (plan.kind == PLAN_ALIGNED && ((S::alu_heavy && (OP == MI355_OP_SUM || OP == MI355_OP_PROD)) ||
-                                      (std::is_same<T, cplxf>::value && OP == MI355_OP_PROD)))
-        bpc = 1 << 20;
-    return launch(k, dim3(grid_for((uint64_t)kBlock * S::unroll, p.nvec, bpc)), st, p, final);
+    return launch(k, dim3(orders_grid<OP, T, NSRC>((const void *)k, plan.kind, p.nvec)), st, p, final);
 }
 
 // Any number of sources >= 2 with a non-null dsts[nsrc - 1]: chained launches

@@ -52,6 +52,26 @@ struct aset {
 
 static int aset_pe (const struct aset *s, int i) { return s->start + i * s->stride; }
 
+/* The active set of an entry point's arguments, checked: inside the job, and
+ * this PE a member. */
+static void aset_init (const char *fn, struct aset *s, int PE_start, int logPE_stride, int PE_size)
+{
+    if (logPE_stride < 0 || logPE_stride > 30 || PE_size < 1 || PE_start < 0 ||
+        PE_start + (long) (PE_size - 1) * (1L << logPE_stride) >= shmemi.npes)
+        shmemi_fatal ("%s: active set (PE_start %d, logPE_stride %d, PE_size %d) outside the %d PEs",
+                      fn, PE_start, logPE_stride, PE_size, shmemi.npes);
+    s->start = PE_start;
+    s->stride = 1 << logPE_stride;
+    s->size = PE_size;
+    s->me = -1;
+    for (int i = 0; i < PE_size; ++i)
+        if (aset_pe (s, i) == shmemi.mype)
+            s->me = i;
+    if (s->me < 0)
+        shmemi_fatal ("%s: PE %d is not in the active set (PE_start %d, logPE_stride %d, PE_size %d)",
+                      fn, shmemi.mype, PE_start, logPE_stride, PE_size);
+}
+
 /* What the call ran (shmemx_last_call_info): called right after the
  * dominant kernel's launch, so the combine layer's last kernel is it.
  * sources/outputs buffers of `bytes` each; extra_alg / extra_peer: bytes
@@ -450,56 +470,9 @@ static int pair_gather (int dtype, size_t es, size_t dst_off, size_t src_off, si
                                  st);
 }
 
-/* P2P shard schedule, dst and src disjoint or identical, with the three
- * barriers as one-block device-barrier kernels on the library stream: five
- * launches queued back to back, one host wait (the last barrier carries the
- * completion flag). The first barrier also orders the sources: each PE's
- * arrival is stream-ordered after its caller's work. */
-static void p2p_range_dev (int op, int dtype, size_t es, size_t dst_off, size_t src_off, size_t n,
-                           const struct aset *s, int ordered, int pair)
-{
-    MI355FusedArgs a;
-    member_args (&a, s, SHMEMI_CHAN_HOST);
-    void *dsts[MI355_FUSED_MAX_MEMBERS];
-    const void *sp[MI355_FUSED_MAX_MEMBERS];
-    size_t nb[MI355_FUSED_MAX_MEMBERS];
-
-    const long long pk = pair ? pair_next (SHMEMI_CHAN_HOST, s) : -1;
-    device_barrier (&a, shmemi.stream); /* every source is ready */
-    shmemi_peer_acquire (shmemi.stream);
-    shmemi_timed_begin ();
-    int rc = fold_shard (op, dtype, es, dst_off, src_off, n, s, ordered, pk, SHMEMI_CHAN_HOST, shmemi.stream);
-    shmemi_timed_end ();
-    if (rc != 0)
-        shmemi_fatal ("combine kernel launch failed (op %d, dtype %d, %d sources, %zu elements): %d", op, dtype,
-                      s->size, n, rc);
-    device_barrier (&a, shmemi.stream); /* every shard is reduced */
-    shmemi_peer_acquire (shmemi.stream);
-    const int k = pair ? 0 : gather_segments (es, dst_off, n, s, ordered, SHMEMI_CHAN_HOST, dsts, sp, nb);
-    if (pair) {
-        shmemi_timed_begin_phase (1);
-        rc = pair_gather (dtype, es, dst_off, src_off, n, s, pk, SHMEMI_CHAN_HOST, shmemi.stream);
-        shmemi_timed_end ();
-        if (rc != 0)
-            shmemi_fatal ("gather kernel launch failed: %d", rc);
-    }
-    if (k > 0) {
-        shmemi_timed_begin_phase (1);
-        rc = mi355_copy_segments (dsts, sp, nb, k, shmemi.stream);
-        shmemi_timed_end ();
-        if (rc != 0)
-            shmemi_fatal ("copy kernel launch failed: %d", rc);
-    }
-    a.host_flag = shmemi.sig_flag; /* peers are done reading us: the call is over */
-    a.epoch = shmemi_next_epoch ();
-    device_barrier (&a, shmemi.stream);
-    if (shmemi_wait_flag (a.epoch) != a.epoch)
-        shmemi_fatal ("device barrier timed out waiting for the other PEs of the active set");
-}
-
 /* Before a host barrier lets peers read this PE's caller-written buffers,
  * the host must know the caller's queued work is done (one signal kernel,
- * shmemi_order_after_caller). Set per call by reduce_impl; the device-flag
+ * shmemi_order_after_caller). Set per call by entry_prologue; the device-flag
  * schedules never need it. */
 static int caller_order_pending;
 
@@ -511,59 +484,175 @@ static void host_order (void)
     }
 }
 
-/* P2P shard schedule (host barriers), dst and src disjoint or identical. */
-static void p2p_range (int op, int dtype, size_t es, size_t dst_off, size_t src_off, size_t n,
-                       const struct aset *s, int ordered, int pair)
+static void stream_barrier (const char *fn, const struct aset *s, hipStream_t st)
 {
-    const void **sp = (const void **) malloc (sizeof (void *) * (size_t) s->size);
-    void **dsts = (void **) malloc (sizeof (void *) * (size_t) s->size);
-    size_t *nb = (size_t *) malloc (sizeof (size_t) * (size_t) s->size);
-    if (sp == NULL || dsts == NULL || nb == NULL)
-        shmemi_fatal ("out of host memory");
-
-    size_t lo, hi;
-    mi355_shard_bounds (n, es, s->size, s->me, &lo, &hi);
-
-    const long long pk = pair ? pair_next (SHMEMI_CHAN_HOST, s) : -1;
-    host_order ();
-    shmemi_barrier_set (s->start, s->stride, s->size); /* every source is ready */
-    if (hi > lo) {
-        shmemi_peer_acquire (shmemi.stream);
-        shmemi_timed_begin ();
-        shmemi_arm_signal ();
-        int rc = fold_shard (op, dtype, es, dst_off, src_off, n, s, ordered, pk, SHMEMI_CHAN_HOST, shmemi.stream);
-        shmemi_timed_end ();
-        if (rc != 0)
-            shmemi_fatal ("combine kernel launch failed (op %d, dtype %d, %d sources, %zu elements): %d", op,
-                          dtype, s->size, n, rc);
-        shmemi_wait_signal ();
-    } else if (pair) { /* an empty shard: fold_shard only clears the next call's NaN word */
-        const int rc = fold_shard (op, dtype, es, dst_off, src_off, n, s, ordered, pk, SHMEMI_CHAN_HOST, shmemi.stream);
-        if (rc != 0)
-            shmemi_fatal ("NaN word clear failed: %d", rc);
-    }
-    shmemi_barrier_set (s->start, s->stride, s->size); /* every shard is reduced */
-    shmemi_peer_acquire (shmemi.stream);
-
-    /* gather the other members' shards: one launch */
-    if (pair) {
-        shmemi_arm_signal ();
-        const int rc = pair_gather (dtype, es, dst_off, src_off, n, s, pk, SHMEMI_CHAN_HOST, shmemi.stream);
-        if (rc != 0)
-            shmemi_fatal ("gather kernel launch failed: %d", rc);
-        shmemi_wait_signal ();
-    } else {
-        const int k = gather_segments (es, dst_off, n, s, ordered, SHMEMI_CHAN_HOST, dsts, sp, nb);
-        copy_wait (dsts, sp, nb, k, 1);
-    }
-    shmemi_barrier_set (s->start, s->stride, s->size); /* peers are done reading us */
-    free (nb);
-    free (dsts);
-    free (sp);
+    if (s->size < 2)
+        return;
+    MI355FusedArgs a;
+    member_args (&a, s, SHMEMI_CHAN_STREAM);
+    const int rc = mi355_device_barrier (&a, st);
+    if (rc != 0)
+        shmemi_fatal ("%s: device barrier launch failed: %d", fn, rc);
 }
 
-/* The multi-launch P2P schedule over [0, n): one round, or (ordered, when the
- * versions outgrow the version area) several, each a complete schedule. */
+static void stream_copy (const char *fn, void *const *dsts, const void *const *srcs, const size_t *nb, int k,
+                         hipStream_t st)
+{
+    for (int base = 0; base < k; base += 64) {
+        const int m = k - base < 64 ? k - base : 64;
+        const int rc = mi355_copy_segments (dsts + base, srcs + base, nb + base, m, st);
+        if (rc != 0)
+            shmemi_fatal ("%s: copy kernel launch failed: %d", fn, rc);
+    }
+}
+
+/* ---------------------------------------------------------------------- */
+/* the multi-launch P2P shard schedule               */
+/* ---------------------------------------------------------------------- */
+/* One round: barrier (every source is ready), the owner's leg on this PE's
+ * shard, barrier (every shard is written), the gather leg, barrier (peers
+ * are done reading this PE). A call picks how the members synchronise and
+ * which two legs run; the two are independent.
+ *
+ *   sync         barrier                       a leg is              timed  channel
+ *   SYNC_HOST    shmemi_barrier_set            signalled and waited  yes    host
+ *   SYNC_DEV     one-block kernel on the       queued; the third     yes    host
+ *                library stream                barrier's flag is the
+ *                                              call's one host wait
+ *   SYNC_STREAM  one-block kernel on the       queued; no host wait  no     stream
+ *                caller's stream               at all (graph capture)
+ *
+ *   legs         owner's leg                              gather leg
+ *   LEGS_FOLD    fold_shard, member order                 segments from the members' targets
+ *   LEGS_ORDERS  fold_shard, every member's order         segments from their version areas
+ *   LEGS_PAIR    fold_shard, this owner's order           pair_gather (NaN-patched)
+ *   LEGS_INSCAN  scan_fold_shard                          segments from their version areas
+ *   LEGS_EXSCAN  scan_fold_shard                          the same; member 0 gathers nothing */
+enum shard_sync { SYNC_HOST, SYNC_DEV, SYNC_STREAM };
+enum shard_legs { LEGS_FOLD, LEGS_ORDERS, LEGS_PAIR, LEGS_INSCAN, LEGS_EXSCAN };
+
+struct shard_call {
+    int op, dtype;
+    size_t es;
+    const struct aset *s;
+    enum shard_legs legs;
+    enum shard_sync sync;
+    hipStream_t st; /* the library stream, or SYNC_STREAM's */
+    const char *fn; /* SYNC_STREAM: the entry point, for its messages */
+};
+
+static int scan_fold_shard (int op, int dtype, size_t es, size_t dst_off, size_t src_off, size_t n,
+                            const struct aset *s, int excl, int chan, hipStream_t st);
+
+/* `last`: SYNC_DEV's barrier carries the completion flag and waits for it */
+static void shard_barrier (const struct shard_call *c, int last)
+{
+    const struct aset *s = c->s;
+    if (c->sync == SYNC_HOST)
+        shmemi_barrier_set (s->start, s->stride, s->size);
+    else if (c->sync == SYNC_DEV)
+        shmemi_dev_barrier (s->start, s->stride, s->size, s->me, last);
+    else
+        stream_barrier (c->fn, s, c->st);
+}
+
+static void shard_round (const struct shard_call *c, size_t dst_off, size_t src_off, size_t n)
+{
+    const struct aset *s = c->s;
+    const int host = c->sync == SYNC_HOST, dev = c->sync == SYNC_DEV;
+    const int chan = c->sync == SYNC_STREAM ? SHMEMI_CHAN_STREAM : SHMEMI_CHAN_HOST;
+    const int pair = c->legs == LEGS_PAIR, scan = c->legs >= LEGS_INSCAN, excl = c->legs == LEGS_EXSCAN;
+    const size_t m = (size_t) s->size; /* sets above MI355_FUSED_MAX_MEMBERS reach SYNC_HOST */
+    void **dsts = (void **) malloc (m * (2 * sizeof (void *) + sizeof (size_t)));
+    if (dsts == NULL)
+        shmemi_fatal ("out of host memory");
+    const void **sp = (const void **) (dsts + m);
+    size_t *nb = (size_t *) (sp + m);
+    size_t lo, hi;
+    mi355_shard_bounds (n, c->es, s->size, s->me, &lo, &hi);
+
+    const long long pk = pair ? pair_next (chan, s) : -1;
+    if (host)
+        host_order ();
+    shard_barrier (c, 0); /* every source is ready; on the device, stream-ordered after the caller's work */
+
+    /* SYNC_HOST launches for a non-empty shard only -- but a pair's empty
+     * shard still clears the next call's NaN word (fold_shard), unsignalled */
+    const int queued = !host || hi > lo;
+    if (queued || pair) {
+        if (queued)
+            shmemi_peer_acquire (c->st);
+        if (queued && c->sync != SYNC_STREAM)
+            shmemi_timed_begin ();
+        if (queued && host)
+            shmemi_arm_signal ();
+        const int rc = scan ? scan_fold_shard (c->op, c->dtype, c->es, dst_off, src_off, n, s, excl, chan, c->st)
+                            : fold_shard (c->op, c->dtype, c->es, dst_off, src_off, n, s, c->legs == LEGS_ORDERS, pk,
+                                          chan, c->st);
+        if (queued && c->sync != SYNC_STREAM)
+            shmemi_timed_end ();
+        if (rc != 0 && c->fn != NULL)
+            shmemi_fatal ("%s: combine kernel launch failed: %d", c->fn, rc);
+        if (rc != 0 && !queued)
+            shmemi_fatal ("NaN word clear failed: %d", rc);
+        if (rc != 0)
+            shmemi_fatal (scan ? "prefix kernel launch failed (op %d, dtype %d, %d members, %zu elements): %d"
+                               : "combine kernel launch failed (op %d, dtype %d, %d sources, %zu elements): %d",
+                          c->op, c->dtype, s->size, n, rc);
+        if (queued && host)
+            shmemi_wait_signal ();
+    }
+    shard_barrier (c, 0); /* every shard is reduced */
+    shmemi_peer_acquire (c->st);
+
+    if (pair) {
+        if (host)
+            shmemi_arm_signal ();
+        if (dev)
+            shmemi_timed_begin_phase (1);
+        const int rc = pair_gather (c->dtype, c->es, dst_off, src_off, n, s, pk, chan, c->st);
+        if (dev)
+            shmemi_timed_end ();
+        if (rc != 0 && c->fn != NULL)
+            shmemi_fatal ("%s: gather kernel launch failed", c->fn);
+        if (rc != 0)
+            shmemi_fatal ("gather kernel launch failed: %d", rc);
+        if (host)
+            shmemi_wait_signal ();
+    } else {
+        /* exscan's member 0 gathers nothing: its target stays as it was */
+        const int k = excl && s->me == 0 ? 0
+                                         : gather_segments (c->es, dst_off, n, s, c->legs != LEGS_FOLD, chan, dsts,
+                                                            sp, nb);
+        if (host) {
+            copy_wait (dsts, sp, nb, k, 1);
+        } else if (c->sync == SYNC_STREAM) {
+            stream_copy (c->fn, dsts, sp, nb, k, c->st);
+        } else if (k > 0) { /* at most MI355_FUSED_MAX_MEMBERS segments: one launch */
+            shmemi_timed_begin_phase (1);
+            const int rc = mi355_copy_segments (dsts, sp, nb, k, c->st);
+            shmemi_timed_end ();
+            if (rc != 0)
+                shmemi_fatal ("copy kernel launch failed: %d", rc);
+        }
+    }
+    shard_barrier (c, 1); /* peers are done reading this target and version area: the call is over */
+    free (dsts);
+}
+
+/* [0, n) in rounds of at most `round` elements, each a complete schedule
+ * (several when the versions outgrow the version area). */
+static void shard_rounds (const struct shard_call *c, size_t dst_off, size_t src_off, size_t n, size_t round)
+{
+    size_t b = 0;
+    do {
+        const size_t cn = n - b < round ? n - b : round;
+        shard_round (c, dst_off + b * c->es, src_off + b * c->es, cn);
+        b += cn;
+    } while (b < n);
+}
+
+/* The multi-launch P2P schedule of a reduction over [0, n). */
 static void p2p_any (int op, int dtype, size_t es, size_t dst_off, size_t src_off, size_t n, const struct aset *s)
 {
     const int pair = nan_pair (op, dtype, s);
@@ -577,15 +666,9 @@ static void p2p_any (int op, int dtype, size_t es, size_t dst_off, size_t src_of
                             : "PE_start order",
                   n, s->size, ordered && n > round ? ", several rounds" : "");
     begin_call (dev ? (n > round ? "p2p-rounds" : "p2p") : (n > round ? "p2p-host-rounds" : "p2p-host"));
-    size_t b = 0;
-    do {
-        const size_t cn = n - b < round ? n - b : round;
-        if (dev)
-            p2p_range_dev (op, dtype, es, dst_off + b * es, src_off + b * es, cn, s, ordered, pair);
-        else
-            p2p_range (op, dtype, es, dst_off + b * es, src_off + b * es, cn, s, ordered, pair);
-        b += cn;
-    } while (b < n);
+    const struct shard_call c = {op, dtype, es, s, pair ? LEGS_PAIR : ordered ? LEGS_ORDERS : LEGS_FOLD,
+                                 dev ? SYNC_DEV : SYNC_HOST, shmemi.stream, NULL};
+    shard_rounds (&c, dst_off, src_off, n, round);
 }
 
 /* The fused one-launch schedule (fused.hip) applies: small enough, few
@@ -1277,62 +1360,64 @@ void shmemi_calibrate_thresholds (int fused, int oneshot)
                   fm, om);
 }
 
-static void reduce_impl (int op, int dtype, const char *fn, void *target, const void *source,
-                         int nreduce, int PE_start, int logPE_stride, int PE_size, long *pSync)
+/* What reduce_impl and scan_impl do first: the argument checks, the n == 0
+ * call, the buffers' kinds (*kt target, *ks source) and the library stream
+ * ordered after the caller's work. 0: the call is over (n == 0). */
+static int entry_prologue (int op, int dtype, const char *fn, void *target, const void *source, int nreduce,
+                           int PE_start, int logPE_stride, int PE_size, long *pSync, struct aset *s, int *kt, int *ks)
 {
     shmemi_init_check (fn);
-    if (logPE_stride < 0 || logPE_stride > 30 || PE_size < 1 || PE_start < 0 ||
-        PE_start + (long) (PE_size - 1) * (1L << logPE_stride) >= shmemi.npes)
-        shmemi_fatal ("%s: active set (PE_start %d, logPE_stride %d, PE_size %d) outside the %d PEs",
-                      fn, PE_start, logPE_stride, PE_size, shmemi.npes);
-    struct aset s = {PE_start, 1 << logPE_stride, PE_size, -1};
-    for (int i = 0; i < PE_size; ++i)
-        if (aset_pe (&s, i) == shmemi.mype)
-            s.me = i;
-    if (s.me < 0)
-        shmemi_fatal ("%s: PE %d is not in the active set (PE_start %d, logPE_stride %d, PE_size %d)",
-                      fn, shmemi.mype, PE_start, logPE_stride, PE_size);
+    aset_init (fn, s, PE_start, logPE_stride, PE_size);
     if (nreduce < 0)
         shmemi_fatal ("%s: nreduce %d < 0", fn, nreduce);
     if (shmemi.debug && pSync != NULL && (pSync[0] != SHMEM_SYNC_VALUE || pSync[1] != SHMEM_SYNC_VALUE))
         shmemi_fatal ("%s: pSync not initialised to SHMEM_SYNC_VALUE", fn);
-
-    const size_t es = mi355_dtype_size (dtype);
-    const size_t n = (size_t) nreduce;
     if (shmemi.debug)
         debug_check (fn, op, dtype, target, source, nreduce, PE_start, logPE_stride, PE_size);
-    if (n == 0) {
+    if (nreduce == 0) {
         begin_call ("barrier-only");
         /* both barriers of reduce-op.c:230,266 still run (host only: no GPU work) */
-        shmemi_barrier_set (s.start, s.stride, s.size);
-        shmemi_barrier_set (s.start, s.stride, s.size);
-        return;
+        shmemi_barrier_set (s->start, s->stride, s->size);
+        shmemi_barrier_set (s->start, s->stride, s->size);
+        return 0;
     }
     if (shmemi.heap == NULL)
         shmemi_fatal ("%s: no GPU: this library reduces on the GPU only (SHMEM_BOOTSTRAP_ONLY set?)", fn);
     if (target == NULL || source == NULL)
         shmemi_fatal ("%s: NULL target or source", fn);
-    const size_t nbytes = n * es;
-    const int kt = ptr_kind (target, nbytes), ks = ptr_kind (source, nbytes);
+    const size_t nbytes = (size_t) nreduce * mi355_dtype_size (dtype);
+    *kt = ptr_kind (target, nbytes);
+    *ks = ptr_kind (source, nbytes);
     /* Device buffers: the library stream is ordered after the caller's
      * null-stream work. The device-flag schedules (fused kernel, device
      * barriers) then learn on the GPU that peers' sources are ready; a
      * schedule with host barriers first waits for that point on the host. */
-    if (kt != PK_HOST || ks != PK_HOST)
+    if (*kt != PK_HOST || *ks != PK_HOST)
         shmemi_order_after_caller (0); /* SHMEM_ENTRY_SYNC */
-    caller_order_pending = s.size > 1 && kt == PK_DEV_SYM && ks == PK_DEV_SYM;
-
-    const int overlap = target != source && ranges_overlap ((size_t) target, (size_t) source, nbytes);
+    caller_order_pending = s->size > 1 && *kt == PK_DEV_SYM && *ks == PK_DEV_SYM;
     if (shmemi_trace_mask & (1u << SHMEMI_LOG_REDUCTION)) {
         static const char *const kind[] = {"host", "device heap", "device, not symmetric"};
+        const int overlap = target != source && ranges_overlap ((size_t) target, (size_t) source, nbytes);
         SHMEMI_TRACE (SHMEMI_LOG_REDUCTION,
                       "%s: nreduce %d, PE_start %d, logPE_stride %d, PE_size %d; target %p (%s), source %p (%s)", fn,
-                      nreduce, PE_start, logPE_stride, PE_size, target, kind[kt], source, kind[ks]);
+                      nreduce, PE_start, logPE_stride, PE_size, target, kind[*kt], source, kind[*ks]);
         /* the reference's overlap trace (reduce-op.c:210-223) */
         SHMEMI_TRACE (SHMEMI_LOG_REDUCTION, "target (%p) and source (%p, size %zu) %s", target, source, nbytes,
                       target == source ? "are the same buffer" : overlap ? "overlap, using temporary target"
                                                                           : "do not overlap");
     }
+    return 1;
+}
+
+static void reduce_impl (int op, int dtype, const char *fn, void *target, const void *source,
+                         int nreduce, int PE_start, int logPE_stride, int PE_size, long *pSync)
+{
+    struct aset s;
+    int kt, ks;
+    if (!entry_prologue (op, dtype, fn, target, source, nreduce, PE_start, logPE_stride, PE_size, pSync, &s, &kt, &ks))
+        return;
+    const size_t es = mi355_dtype_size (dtype), n = (size_t) nreduce, nbytes = n * es;
+    const int overlap = target != source && ranges_overlap ((size_t) target, (size_t) source, nbytes);
     /* RCCL by request, or whenever the init self-test found peer heap reads
      * broken (whatever the selected algorithm): the pairs RCCL has still run */
     const int use_rccl = (shmemi.algorithm == SHMEMX_REDUCE_RCCL || shmemi.p2p_broken) && s.size == shmemi.npes &&
@@ -1410,47 +1495,12 @@ static void stream_begin (const char *fn)
 
 static void stream_aset (const char *fn, struct aset *s, int PE_start, int logPE_stride, int PE_size)
 {
-    if (logPE_stride < 0 || logPE_stride > 30 || PE_size < 1 || PE_start < 0 ||
-        PE_start + (long) (PE_size - 1) * (1L << logPE_stride) >= shmemi.npes)
-        shmemi_fatal ("%s: active set (PE_start %d, logPE_stride %d, PE_size %d) outside the %d PEs",
-                      fn, PE_start, logPE_stride, PE_size, shmemi.npes);
-    s->start = PE_start;
-    s->stride = 1 << logPE_stride;
-    s->size = PE_size;
-    s->me = -1;
-    for (int i = 0; i < PE_size; ++i)
-        if (aset_pe (s, i) == shmemi.mype)
-            s->me = i;
-    if (s->me < 0)
-        shmemi_fatal ("%s: PE %d is not in the active set (PE_start %d, logPE_stride %d, PE_size %d)",
-                      fn, shmemi.mype, PE_start, logPE_stride, PE_size);
+    aset_init (fn, s, PE_start, logPE_stride, PE_size);
     if (PE_size > MI355_FUSED_MAX_MEMBERS || shmemi.npes > MI355_SIG_RSDONE)
         shmemi_fatal ("%s: stream-ordered collectives take at most %d PEs per active set (of at most %d)",
                       fn, MI355_FUSED_MAX_MEMBERS, MI355_SIG_RSDONE);
     if (PE_size > 1 && (shmemi.sigmem == NULL || shmemi.p2p_broken || shmemi.sig_broken))
         shmemi_fatal ("%s: peer GPU memory failed the init self-test", fn);
-}
-
-static void stream_barrier (const char *fn, const struct aset *s, hipStream_t st)
-{
-    if (s->size < 2)
-        return;
-    MI355FusedArgs a;
-    member_args (&a, s, SHMEMI_CHAN_STREAM);
-    const int rc = mi355_device_barrier (&a, st);
-    if (rc != 0)
-        shmemi_fatal ("%s: device barrier launch failed: %d", fn, rc);
-}
-
-static void stream_copy (const char *fn, void *const *dsts, const void *const *srcs, const size_t *nb, int k,
-                         hipStream_t st)
-{
-    for (int base = 0; base < k; base += 64) {
-        const int m = k - base < 64 ? k - base : 64;
-        const int rc = mi355_copy_segments (dsts + base, srcs + base, nb + base, m, st);
-        if (rc != 0)
-            shmemi_fatal ("%s: copy kernel launch failed: %d", fn, rc);
-    }
 }
 
 static void reduce_on_stream (int op, int dtype, const char *fn, void *target, const void *source, int nreduce,
@@ -1510,33 +1560,13 @@ static void reduce_on_stream (int op, int dtype, const char *fn, void *target, c
             begin_call (a.oneshot ? "stream-fused-oneshot" : "stream-fused-twoshot");
             note_fused (s.size, a.ordered, a.oneshot, n, es, mi355_last_kernel ());
         } else {
-            void *dsts[MI355_FUSED_MAX_MEMBERS];
-            const void *sp[MI355_FUSED_MAX_MEMBERS];
-            size_t nb[MI355_FUSED_MAX_MEMBERS];
             const int pair = nan_pair (op, dtype, &s);
             const int ord = ordered && !pair;
             const size_t round = ord ? ordered_round_elems (es, s.size) : n;
             begin_call (n > round ? "stream-p2p-rounds" : "stream-p2p");
-            for (size_t b = 0; b < n; b += round) {
-                const size_t cn = n - b < round ? n - b : round;
-                const size_t d0 = dst_off + b * es, s0 = src_off + b * es;
-                const long long pk = pair ? pair_next (SHMEMI_CHAN_STREAM, &s) : -1;
-                stream_barrier (fn, &s, st); /* every source is ready */
-                shmemi_peer_acquire (st);
-                const int rc = fold_shard (op, dtype, es, d0, s0, cn, &s, ord, pk, SHMEMI_CHAN_STREAM, st);
-                if (rc != 0)
-                    shmemi_fatal ("%s: combine kernel launch failed: %d", fn, rc);
-                stream_barrier (fn, &s, st); /* every shard is reduced */
-                shmemi_peer_acquire (st);
-                if (pair) {
-                    if (pair_gather (dtype, es, d0, s0, cn, &s, pk, SHMEMI_CHAN_STREAM, st) != 0)
-                        shmemi_fatal ("%s: gather kernel launch failed", fn);
-                } else {
-                    const int k = gather_segments (es, d0, cn, &s, ord, SHMEMI_CHAN_STREAM, dsts, sp, nb);
-                    stream_copy (fn, dsts, sp, nb, k, st);
-                }
-                stream_barrier (fn, &s, st); /* peers are done reading this target and version area */
-            }
+            const struct shard_call c = {op, dtype, es, &s, pair ? LEGS_PAIR : ord ? LEGS_ORDERS : LEGS_FOLD,
+                                         SYNC_STREAM, st, fn};
+            shard_rounds (&c, dst_off, src_off, n, round);
         }
     }
 }
@@ -1646,15 +1676,12 @@ SHMEMX_REDUCE_TYPE (bfloat16, MI355_BFLOAT16)
  * There is one order, so the result-order setting does not apply, and the
  * algorithm setting does not change the bits: every request runs one of
  *
- *   shard    (up to MI355_ORDERS_MAX_SOURCES members) the every-member-order
- *            schedule with another kernel: barrier; the owner of shard i
- *            reads every member's source shard once and writes EVERY prefix
- *            of it (mi355_combine_prefix) -- its own into its target shard,
- *            member q's into slot q of its version area; barrier; every
- *            member gathers its version of the other shards
- *            (gather_segments, unchanged); barrier. Device-flag or host
- *            barriers, and several rounds when the versions outgrow the
- *            version area, as p2p_any.
+ *   shard    (up to MI355_ORDERS_MAX_SOURCES members) the shard schedule
+ *            (shard_round) with the LEGS_INSCAN / LEGS_EXSCAN legs: the owner
+ *            of shard i reads every member's source shard once and writes
+ *            EVERY prefix of it (mi355_combine_prefix) -- its own into its
+ *            target shard, member q's into slot q of its version area, from
+ *            which q gathers it.
  *   direct   (larger sets, or SHMEM_SCAN_DIRECT=1, a testing aid) between two
  *            host barriers member j folds the whole arrays of members 0 .. j
  *            with mi355_combine: j + 1 times the reads instead of one.
@@ -1713,85 +1740,6 @@ static int scan_fold_shard (int op, int dtype, size_t es, size_t dst_off, size_t
     return rc;
 }
 
-/* exscan's member 0 gathers nothing: its target stays as it was */
-static int scan_gather (size_t es, size_t dst_off, size_t n, const struct aset *s, int excl, int chan, void **dsts,
-                        const void **sp, size_t *nb)
-{
-    if (excl && s->me == 0)
-        return 0;
-    return gather_segments (es, dst_off, n, s, 1, chan, dsts, sp, nb);
-}
-
-/* The shard schedule with device-flag barriers (p2p_range_dev's shape) */
-static void scan_range_dev (int op, int dtype, size_t es, size_t dst_off, size_t src_off, size_t n,
-                            const struct aset *s, int excl)
-{
-    MI355FusedArgs a;
-    member_args (&a, s, SHMEMI_CHAN_HOST);
-    void *dsts[MI355_FUSED_MAX_MEMBERS];
-    const void *sp[MI355_FUSED_MAX_MEMBERS];
-    size_t nb[MI355_FUSED_MAX_MEMBERS];
-
-    device_barrier (&a, shmemi.stream); /* every source is ready */
-    shmemi_peer_acquire (shmemi.stream);
-    shmemi_timed_begin ();
-    int rc = scan_fold_shard (op, dtype, es, dst_off, src_off, n, s, excl, SHMEMI_CHAN_HOST, shmemi.stream);
-    shmemi_timed_end ();
-    if (rc != 0)
-        shmemi_fatal ("prefix kernel launch failed (op %d, dtype %d, %d members, %zu elements): %d", op, dtype,
-                      s->size, n, rc);
-    device_barrier (&a, shmemi.stream); /* every shard's prefixes are written */
-    shmemi_peer_acquire (shmemi.stream);
-    const int k = scan_gather (es, dst_off, n, s, excl, SHMEMI_CHAN_HOST, dsts, sp, nb);
-    if (k > 0) {
-        shmemi_timed_begin_phase (1);
-        rc = mi355_copy_segments (dsts, sp, nb, k, shmemi.stream);
-        shmemi_timed_end ();
-        if (rc != 0)
-            shmemi_fatal ("copy kernel launch failed: %d", rc);
-    }
-    a.host_flag = shmemi.sig_flag; /* peers are done reading us: the call is over */
-    a.epoch = shmemi_next_epoch ();
-    device_barrier (&a, shmemi.stream);
-    if (shmemi_wait_flag (a.epoch) != a.epoch)
-        shmemi_fatal ("device barrier timed out waiting for the other PEs of the active set");
-}
-
-/* The shard schedule with host barriers (p2p_range's shape) */
-static void scan_range (int op, int dtype, size_t es, size_t dst_off, size_t src_off, size_t n,
-                        const struct aset *s, int excl)
-{
-    const void **sp = (const void **) malloc (sizeof (void *) * (size_t) s->size);
-    void **dsts = (void **) malloc (sizeof (void *) * (size_t) s->size);
-    size_t *nb = (size_t *) malloc (sizeof (size_t) * (size_t) s->size);
-    if (sp == NULL || dsts == NULL || nb == NULL)
-        shmemi_fatal ("out of host memory");
-    size_t lo, hi;
-    mi355_shard_bounds (n, es, s->size, s->me, &lo, &hi);
-
-    host_order ();
-    shmemi_barrier_set (s->start, s->stride, s->size); /* every source is ready */
-    if (hi > lo) {
-        shmemi_peer_acquire (shmemi.stream);
-        shmemi_timed_begin ();
-        shmemi_arm_signal ();
-        const int rc = scan_fold_shard (op, dtype, es, dst_off, src_off, n, s, excl, SHMEMI_CHAN_HOST, shmemi.stream);
-        shmemi_timed_end ();
-        if (rc != 0)
-            shmemi_fatal ("prefix kernel launch failed (op %d, dtype %d, %d members, %zu elements): %d", op, dtype,
-                          s->size, n, rc);
-        shmemi_wait_signal ();
-    }
-    shmemi_barrier_set (s->start, s->stride, s->size); /* every shard's prefixes are written */
-    shmemi_peer_acquire (shmemi.stream);
-    const int k = scan_gather (es, dst_off, n, s, excl, SHMEMI_CHAN_HOST, dsts, sp, nb);
-    copy_wait (dsts, sp, nb, k, 1);
-    shmemi_barrier_set (s->start, s->stride, s->size); /* peers are done reading us */
-    free (nb);
-    free (dsts);
-    free (sp);
-}
-
 /* The direct schedule: this member's fold of the whole arrays; dst must not
  * overlap any source (scan_symmetric routes overlaps through scratch). */
 static void scan_direct (int op, int dtype, size_t es, size_t dst_off, size_t src_off, size_t n, const struct aset *s,
@@ -1832,15 +1780,9 @@ static void scan_any (int op, int dtype, size_t es, size_t dst_off, size_t src_o
                                         "(%zu elements, %d members%s)", dev ? "device" : "host", n, s->size,
                   n > round ? ", several rounds" : "");
     begin_call (dev ? (n > round ? "scan-p2p-rounds" : "scan-p2p") : (n > round ? "scan-p2p-host-rounds" : "scan-p2p-host"));
-    size_t b = 0;
-    do {
-        const size_t cn = n - b < round ? n - b : round;
-        if (dev)
-            scan_range_dev (op, dtype, es, dst_off + b * es, src_off + b * es, cn, s, excl);
-        else
-            scan_range (op, dtype, es, dst_off + b * es, src_off + b * es, cn, s, excl);
-        b += cn;
-    } while (b < n);
+    const struct shard_call c = {op, dtype, es, s, excl ? LEGS_EXSCAN : LEGS_INSCAN, dev ? SYNC_DEV : SYNC_HOST,
+                                 shmemi.stream, NULL};
+    shard_rounds (&c, dst_off, src_off, n, round);
 }
 
 static void scan_symmetric (int op, int dtype, size_t es, size_t dst_off, size_t src_off, size_t n,
@@ -1921,55 +1863,14 @@ static void scan_staged (int op, int dtype, void *target, const void *source, si
 static void scan_impl (int op, int dtype, int excl, const char *fn, void *target, const void *source, int nreduce,
                        int PE_start, int logPE_stride, int PE_size, long *pSync)
 {
-    shmemi_init_check (fn);
-    if (logPE_stride < 0 || logPE_stride > 30 || PE_size < 1 || PE_start < 0 ||
-        PE_start + (long) (PE_size - 1) * (1L << logPE_stride) >= shmemi.npes)
-        shmemi_fatal ("%s: active set (PE_start %d, logPE_stride %d, PE_size %d) outside the %d PEs", fn, PE_start,
-                      logPE_stride, PE_size, shmemi.npes);
-    struct aset s = {PE_start, 1 << logPE_stride, PE_size, -1};
-    for (int i = 0; i < PE_size; ++i)
-        if (aset_pe (&s, i) == shmemi.mype)
-            s.me = i;
-    if (s.me < 0)
-        shmemi_fatal ("%s: PE %d is not in the active set (PE_start %d, logPE_stride %d, PE_size %d)", fn,
-                      shmemi.mype, PE_start, logPE_stride, PE_size);
-    if (nreduce < 0)
-        shmemi_fatal ("%s: nreduce %d < 0", fn, nreduce);
-    if (shmemi.debug && pSync != NULL && (pSync[0] != SHMEM_SYNC_VALUE || pSync[1] != SHMEM_SYNC_VALUE))
-        shmemi_fatal ("%s: pSync not initialised to SHMEM_SYNC_VALUE", fn);
-
-    const size_t es = mi355_dtype_size (dtype);
-    const size_t n = (size_t) nreduce;
-    if (shmemi.debug)
-        debug_check (fn, op, dtype, target, source, nreduce, PE_start, logPE_stride, PE_size);
-    if (n == 0) {
-        begin_call ("barrier-only");
-        shmemi_barrier_set (s.start, s.stride, s.size);
-        shmemi_barrier_set (s.start, s.stride, s.size);
+    struct aset s;
+    int kt, ks;
+    if (!entry_prologue (op, dtype, fn, target, source, nreduce, PE_start, logPE_stride, PE_size, pSync, &s, &kt, &ks))
         return;
-    }
-    if (shmemi.heap == NULL)
-        shmemi_fatal ("%s: no GPU: this library reduces on the GPU only (SHMEM_BOOTSTRAP_ONLY set?)", fn);
-    if (target == NULL || source == NULL)
-        shmemi_fatal ("%s: NULL target or source", fn);
-    const size_t nbytes = n * es;
-    const int kt = ptr_kind (target, nbytes), ks = ptr_kind (source, nbytes);
     if (kt == PK_DEV_OTHER || ks == PK_DEV_OTHER)
         shmemi_fatal ("%s: %s is device memory outside the symmetric heap; the scan collectives take device-heap "
                       "(shmemx_malloc_device) and host objects only", fn, kt == PK_DEV_OTHER ? "target" : "source");
-    if (kt != PK_HOST || ks != PK_HOST)
-        shmemi_order_after_caller (0); /* SHMEM_ENTRY_SYNC */
-    caller_order_pending = s.size > 1 && kt == PK_DEV_SYM && ks == PK_DEV_SYM;
-    if (shmemi_trace_mask & (1u << SHMEMI_LOG_REDUCTION)) {
-        static const char *const kind[] = {"host", "device heap", "device, not symmetric"};
-        const int overlap = target != source && ranges_overlap ((size_t) target, (size_t) source, nbytes);
-        SHMEMI_TRACE (SHMEMI_LOG_REDUCTION,
-                      "%s: nreduce %d, PE_start %d, logPE_stride %d, PE_size %d; target %p (%s), source %p (%s)", fn,
-                      nreduce, PE_start, logPE_stride, PE_size, target, kind[kt], source, kind[ks]);
-        SHMEMI_TRACE (SHMEMI_LOG_REDUCTION, "target (%p) and source (%p, size %zu) %s", target, source, nbytes,
-                      target == source ? "are the same buffer" : overlap ? "overlap, using temporary target"
-                                                                          : "do not overlap");
-    }
+    const size_t es = mi355_dtype_size (dtype), n = (size_t) nreduce;
     if (kt == PK_DEV_SYM && ks == PK_DEV_SYM) {
         scan_symmetric (op, dtype, es, shmemi_heap_offset (target), shmemi_heap_offset (source), n, &s, excl);
         return;

@@ -137,6 +137,17 @@ def run_datamove(shm, c, me, da, db, ha, hb, results):
     results[str(c["id"])] = got
 
 
+def golden_source(c, op, dtype, n, member):
+    """Member `member`'s row of the committed fixture (tests/golden/) a case
+    names; "family": "nan_" picks the NaN-payload families, "golden_at": its n
+    elements from that column on instead of the whole row."""
+    g = np.load(os.path.join(HERE, "golden", f"golden_{c.get('family', '')}{op}_{dtype}.npz"))
+    x = g[f"in_{c['golden']}"][member]
+    if "golden_at" in c:
+        x = x[c["golden_at"]:c["golden_at"] + n]
+    return np.ascontiguousarray(x)
+
+
 def run_stream(shm, c, me, da, db, results):
     """kind "stream": a chain of `chain` stream-ordered reductions on one HIP
     stream, buf[i+1] <- reduce(buf[i]), enqueued back to back with no host
@@ -176,7 +187,8 @@ def run_stream(shm, c, me, da, db, results):
             shm.graph_destroy(graph, exe)
         else:
             if n:
-                shm.put(bufs[0], source(op, dtype, n, c["seed"], me))
+                shm.put(bufs[0], golden_source(c, op, dtype, n, members(*mine).index(me)) if "golden" in c
+                        else source(op, dtype, n, c["seed"], me))
                 if c.get("mixed"):
                     shm.put(da, source(op, dtype, n, c["seed"] + 1, me))
             enqueue()
@@ -187,6 +199,7 @@ def run_stream(shm, c, me, da, db, results):
             shm.stream_sync(st)
             for i in range(1, k + 1):
                 results[f"{c['id']}_{i}"] = shm.get(bufs[i], n, dtype)
+            results[f"{c['id']}_schedule"] = np.array([shm.last_call_info()["schedule"]])
         shm.stream_destroy(st)
     shm.free_device(base)
 
@@ -313,9 +326,7 @@ def main():
         op, dtype, n = c["op"], c["dtype"], c["n"]
         es = np.dtype(shmem_reduce.NP[dtype]).itemsize
         if "golden" in c:  # the committed fixture's inputs (tests/golden/), member i's row
-            fam = c.get("family", "")   # "nan_": the NaN-payload families
-            g = np.load(os.path.join(HERE, "golden", f"golden_{fam}{op}_{dtype}.npz"))
-            x = np.ascontiguousarray(g[f"in_{c['golden']}"][members(*mine).index(me)])
+            x = golden_source(c, op, dtype, n, members(*mine).index(me))
         else:
             x = source(op, dtype, n, c["seed"], me)
         mode = c["mode"]
