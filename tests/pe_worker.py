@@ -148,13 +148,48 @@ def golden_source(c, op, dtype, n, member):
     return np.ascontiguousarray(x)
 
 
+def stream_input(c, kind, seed, mine, me):
+    """One member's first source of a stream case: its row of the golden
+    fixture the case names, else what `kind` says ("inputs": "finite" | "nan",
+    tests/_inputs.py; without "inputs" the seeded source); for the 16-bit
+    floats member i of the model's special-value sources (tests/_half_ref.py),
+    as their bit patterns."""
+    op, dtype, n = c["op"], c["dtype"], c["n"]
+    mem = members(*mine)
+    if "golden" in c:
+        return golden_source(c, op, dtype, n, mem.index(me))
+    if dtype in shmem_reduce.SHMEMX_DTYPES:
+        import _half_ref
+        return _half_ref.sources(dtype, len(mem), n, seed)[mem.index(me)]
+    import _inputs
+    return _inputs.by_kind(kind, op, dtype, n, seed, me)
+
+
+def stream_np(dtype):
+    return np.uint16 if dtype in shmem_reduce.SHMEMX_DTYPES else shmem_reduce.NP[dtype]
+
+
+def check_thresholds(shm, c):
+    """"thresholds": [fused_max, oneshot_max] -- what the case's sizes were
+    derived from must be what the library runs with"""
+    if "thresholds" in c:
+        assert list(shm.thresholds()) == list(c["thresholds"]), (shm.thresholds(), c["thresholds"])
+
+
 def run_stream(shm, c, me, da, db, results):
     """kind "stream": a chain of `chain` stream-ordered reductions on one HIP
     stream, buf[i+1] <- reduce(buf[i]), enqueued back to back with no host
     wait; or (graph > 0) the same chain captured once into a HIP graph and
-    replayed `graph` times with a fresh input each time."""
+    replayed `graph` times with a fresh input each time. "inplace": every call
+    of the chain has target = source = buf[0], and only the final buffer is
+    saved (as step `chain`). "inputs": the kind of data ("finite" | "nan") of
+    the chain's start, or one entry per graph replay; "eager_after": after the
+    replays, one eager chain per entry on the same buffers. The schedule the
+    case's last call reported is saved for every case."""
     op, dtype, n, k = c["op"], c["dtype"], c["n"], c["chain"]
-    es = np.dtype(shmem_reduce.NP[dtype]).itemsize
+    check_thresholds(shm, c)
+    npt = stream_np(dtype)
+    es = np.dtype(npt).itemsize
     off = c.get("offset", 0)                      # elements off 16-byte alignment
     stride = ((n + off) * es + 255) // 256 * 256 + 256
     base = shm.malloc_device(stride * (k + 1))    # collective: every PE allocates
@@ -164,7 +199,9 @@ def run_stream(shm, c, me, da, db, results):
             mine = s
     if mine is not None:
         shm.set_order(c.get("order", "reference"))
-        bufs = [base + i * stride + off * es for i in range(k + 1)]
+        inplace = bool(c.get("inplace"))
+        bufs = [base + (0 if inplace else i) * stride + off * es for i in range(k + 1)]
+        kinds = c.get("inputs", ["default"])
         st = shm.stream_create()
 
         def enqueue():
@@ -178,28 +215,68 @@ def run_stream(shm, c, me, da, db, results):
             shm.capture_begin(st)
             enqueue()
             graph, exe = shm.capture_end(st)
+            # begin_call runs when the call is made: at capture time
+            results[f"{c['id']}_schedule"] = np.array([shm.last_call_info()["schedule"]])
             for r in range(replays):
                 if n:
-                    shm.put(bufs[0], source(op, dtype, n, c["seed"] + r, me))
+                    shm.put(bufs[0], stream_input(c, kinds[r % len(kinds)], c["seed"] + r, mine, me))
                 shm.graph_launch(exe, st)
                 shm.stream_sync(st)
-                results[f"{c['id']}_r{r}"] = shm.get(bufs[k], n, dtype)
+                results[f"{c['id']}_r{r}"] = shm.get(bufs[k], n, npt)
             shm.graph_destroy(graph, exe)
+            for j, kind in enumerate(c.get("eager_after", [])):
+                shm.put(bufs[0], stream_input(c, kind, c["seed"] + replays + j, mine, me))
+                enqueue()
+                shm.stream_sync(st)
+                results[f"{c['id']}_e{j}"] = shm.get(bufs[k], n, npt)
         else:
             if n:
-                shm.put(bufs[0], golden_source(c, op, dtype, n, members(*mine).index(me)) if "golden" in c
-                        else source(op, dtype, n, c["seed"], me))
+                shm.put(bufs[0], stream_input(c, kinds[0], c["seed"], mine, me))
                 if c.get("mixed"):
-                    shm.put(da, source(op, dtype, n, c["seed"] + 1, me))
+                    shm.put(da, stream_input(c, kinds[0], c["seed"] + 1, mine, me))
             enqueue()
+            results[f"{c['id']}_schedule"] = np.array([shm.last_call_info()["schedule"]])
             if c.get("mixed"):
                 # a host-side call while the stream chain is in flight
                 shm.to_all(op, dtype, db, da, n, *mine)
-                results[f"{c['id']}_host"] = shm.get(db, n, dtype)
+                results[f"{c['id']}_host"] = shm.get(db, n, npt)
             shm.stream_sync(st)
-            for i in range(1, k + 1):
-                results[f"{c['id']}_{i}"] = shm.get(bufs[i], n, dtype)
-            results[f"{c['id']}_schedule"] = np.array([shm.last_call_info()["schedule"]])
+            for i in range(k if inplace else 1, k + 1):
+                results[f"{c['id']}_{i}"] = shm.get(bufs[i], n, npt)
+        shm.stream_destroy(st)
+    shm.free_device(base)
+
+
+def run_stream_seq(shm, c, me, results):
+    """kind "stream_seq": the independent stream-ordered calls of c["calls"]
+    (each its own op, dtype, n, "inputs" kind or golden row, "inplace" flag
+    and buffers) enqueued back to back on one stream with no host wait, one
+    stream_sync, then every target saved under its call's id, and the schedule
+    each call reported."""
+    check_thresholds(shm, c)
+    calls = c["calls"]
+    sizes = [(q["n"] * np.dtype(stream_np(q["dtype"])).itemsize + 255) // 256 * 256 + 256 for q in calls]
+    base = shm.malloc_device(2 * sum(sizes))      # collective: every PE allocates
+    mine = None
+    for s in c["sets"]:
+        if me in members(*s):
+            mine = s
+    if mine is not None:
+        shm.set_order(c.get("order", "reference"))
+        st = shm.stream_create()
+        at, where = base, []
+        for q, size in zip(calls, sizes):
+            src, dst = at, at if q.get("inplace") else at + size
+            at += 2 * size
+            where.append((src, dst))
+            q = dict(q, chain=1)
+            shm.put(src, stream_input(q, q.get("inputs", ["default"])[0], q["seed"], mine, me))
+        for q, (src, dst) in zip(calls, where):
+            shm.to_all_on_stream(q["op"], q["dtype"], dst, src, q["n"], *mine, st)
+            results[f"{q['id']}_schedule"] = np.array([shm.last_call_info()["schedule"]])
+        shm.stream_sync(st)
+        for q, (src, dst) in zip(calls, where):
+            results[str(q["id"])] = shm.get(dst, q["n"], stream_np(q["dtype"]))
         shm.stream_destroy(st)
     shm.free_device(base)
 
@@ -293,7 +370,7 @@ def main():
     shm = shmem_reduce.Shmem()
     shm.init()
     me = shm.my_pe()
-    maxb = max(max(c["n"] + 16, c.get("cap", 0)) * 16 if c.get("kind") not in ("config", "big") else 4096
+    maxb = max(max(c["n"] + 16, c.get("cap", 0)) * 16 if c.get("kind") not in ("config", "big", "stream_seq") else 4096
                for c in spec["cases"])
     da, db = shm.malloc_device(maxb), shm.malloc_device(maxb)
     ha, hb = shm.malloc(maxb), shm.malloc(maxb)
@@ -313,6 +390,9 @@ def main():
             continue
         if c.get("kind") == "stream":
             run_stream(shm, c, me, da, db, results)
+            continue
+        if c.get("kind") == "stream_seq":
+            run_stream_seq(shm, c, me, results)
             continue
         if c.get("kind", "reduce") != "reduce":
             run_datamove(shm, c, me, da, db, ha, hb, results)

@@ -20,12 +20,13 @@ from test_gpu_multipe import members, run_pes
 pytestmark = [pytest.mark.gpu, pytest.mark.multipe]
 
 
-def chain_want(op, dtype, n, seed, mem, k, pe, order="reference"):
-    """Step results 1..k on member `pe` of `mem`."""
+def chain_want(op, dtype, n, seed, mem, k, pe, order="reference", xs=None):
+    """Step results 1..k on member `pe` of `mem`; xs: the members' first
+    sources where they are not the seeded ones."""
     def step(xs):
         return [oracle.reduce_pe(op, dtype, xs, i if order == "reference" else 0) for i in range(len(mem))]
     ys = []
-    y = step([source(op, dtype, n, seed, q) for q in mem])
+    y = step([source(op, dtype, n, seed, q) for q in mem] if xs is None else xs)
     ys.append(y[mem.index(pe)])
     for _ in range(k - 1):
         y = step(y)
