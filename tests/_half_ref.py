@@ -11,6 +11,8 @@ kernels are held to, bit for bit. Elements are uint16 bit patterns throughout.
   fold             PE q receives (((src_q op src_m0) op src_m1) ...), m0 < m1 < ...
                    the members other than q
 """
+import functools
+
 import numpy as np
 
 TYPES = ("half", "bfloat16")
@@ -126,6 +128,51 @@ def exhaustive_pairs(dtype):
     near = exponent_near(dtype, rng, a)
     b[1::2] = near[1::2]
     return a, b
+
+
+def product_pairs(dtype):
+    """every 16-bit pattern with 64 partners each, aimed at the product's
+    edges: partner i's exponent field puts the product's at one of four
+    targets (around 1.0, the smallest normal, half the smallest subnormal, the
+    last finite binade) plus a jitter in [-2, 2]; mantissa and sign random"""
+    mant, bias, emax_field = (10, 15, 31) if dtype == "half" else (7, 127, 255)
+    rng = np.random.default_rng(4321)
+    a = np.repeat(np.arange(1 << 16, dtype=np.uint16), 64)
+    target = np.array([bias, 1, -mant, emax_field - 1], dtype=np.int64)[np.arange(a.size) % 4]
+    target += rng.integers(-2, 3, a.size)
+    ea = (a.astype(np.int64) & 0x7FFF) >> mant
+    eb = np.clip(target + bias - np.maximum(ea, 1), 0, emax_field - 1)
+    rest = rng.integers(0, 1 << mant, a.size) | (rng.integers(0, 2, a.size) << 15)
+    return a, ((eb << mant) | rest).astype(np.uint16)
+
+
+PAIR_SETS = {"exhaustive": exhaustive_pairs, "product": product_pairs}
+
+
+@functools.lru_cache(maxsize=None)
+def pair_set(name, dtype):
+    """(a, b) of PAIR_SETS[name], generated once per process and read-only"""
+    a, b = PAIR_SETS[name](dtype)
+    a.setflags(write=False)
+    b.setflags(write=False)
+    return a, b
+
+
+def third_operand(dtype, a, b, seed=0):
+    """a third array for three-step chains on the pairs (a, b): seeded random
+    bit patterns, every second element with an exponent field within 3 of that
+    of step("sum", a, b) (so the second sum rounds, cancels or overflows), every
+    64th element a NaN or an infinity of the special table"""
+    rng = np.random.default_rng(8642 + seed)
+    s = step("sum", dtype, a, b)
+    c = rng.integers(0, 1 << 16, s.size, dtype=np.uint16)
+    near = exponent_near(dtype, rng, s)
+    c[1::2] = near[1::2]
+    t = special_table(dtype)
+    inf = 0x7FFF & ~((1 << (10 if dtype == "half" else 7)) - 1)
+    nonfinite = t[(t & 0x7FFF) >= inf]
+    c[::64] = nonfinite[rng.integers(0, nonfinite.size, c[::64].size)]
+    return c
 
 
 def sources(dtype, nsrc, n, seed):

@@ -10,7 +10,9 @@ usage: _half_worker.py SPEC.json   (identity from SHMEM_PE / SHMEM_NPES)
 A case: {"id", "op", "dtype", "n", "set": [PE_start, logPE_stride, PE_size],
 "mode": dev | inplace | host, "order": reference | pe_start, "algorithm":
 auto | p2p | exact | rccl, "stream": bool, "seed"}. Member i's source is
-_half_ref.sources(dtype, PE_size, n, seed)[i]. A "torch" case: {"id", "torch":
+_half_ref.sources(dtype, PE_size, n, seed)[i], or with "inputs": exhaustive |
+product (two members) the first n of a (member 0) and b (member 1) of that
+pair set (_half_ref.PAIR_SETS). A "torch" case: {"id", "torch":
 float16 | bfloat16, "op", "n", "heap": bool, "seed"} reduces torch tensors over
 all PEs -- from the caching allocator through to_all_tensors, or (heap) a
 heap_tensor through the stream-ordered call.
@@ -58,7 +60,11 @@ def run_reduce(shm, c, me, bufs, failures, schedules):
     if me not in mem:
         return
     op, dtype, n = c["op"], c["dtype"], c["n"]
-    srcs = R.sources(dtype, len(mem), n, c["seed"])
+    if "inputs" in c:
+        assert len(mem) == 2, c
+        srcs = [s[:n] for s in R.pair_set(c["inputs"], dtype)]
+    else:
+        srcs = R.sources(dtype, len(mem), n, c["seed"])
     x = srcs[mem.index(me)]
     mode = c["mode"]
     host = mode == "host"

@@ -9,7 +9,9 @@ usage: _scan_worker.py SPEC.json   (identity from SHMEM_PE / SHMEM_NPES)
 A case: {"id", "op", "dtype", "n", "set": [PE_start, logPE_stride, PE_size],
 "excl": bool, "mode": dev | inplace | host | overlap_up | overlap_down, "seed",
 "algorithm": auto | p2p | exact | rccl}. Member i's source is
-_scan_ref.sources(op, dtype, PE_size, n, seed)[i]. overlap_up / overlap_down:
+_scan_ref.sources(op, dtype, PE_size, n, seed)[i] (with "inputs": exhaustive |
+product, two members of a 16-bit float type: the first n of a and b of that
+pair set of tests/_half_ref.py). overlap_up / overlap_down:
 the target starts 16 elements above / below the source in one buffer. A
 "torch" case {"id", "torch": float32 | bfloat16, "op", "n", "excl", "seed"}
 runs Shmem.scan_tensors on heap_tensors over all PEs.
@@ -27,6 +29,7 @@ ROOT = os.path.dirname(HERE)
 for p in (HERE, os.path.join(ROOT, "osss-gasnet_amd"), os.path.join(ROOT, "oracle")):
     sys.path.insert(0, p)
 
+import _half_ref  # noqa: E402
 import _scan_ref as S  # noqa: E402
 import oracle  # noqa: E402
 import shmem_reduce  # noqa: E402
@@ -80,7 +83,10 @@ def run_scan(shm, c, me, bufs, out):
     j = mem_pes.index(me)
     op, dtype, n, excl, mode = c["op"], c["dtype"], c["n"], bool(c.get("excl")), c["mode"]
     es = np.dtype(S.NP[dtype]).itemsize
-    srcs = S.sources(op, dtype, len(mem_pes), n, c["seed"])
+    if "inputs" in c:    # the 16-bit floats' pair sets: a is member 0's source, b member 1's
+        srcs = [s[:n] for s in _half_ref.pair_set(c["inputs"], dtype)]
+    else:
+        srcs = S.sources(op, dtype, len(mem_pes), n, c["seed"])
     x = srcs[j]
     m = Mem(shm, mode == "host")
     a, b = (bufs["ha"], bufs["hb"]) if mode == "host" else (bufs["da"], bufs["db"])

@@ -4,7 +4,9 @@ implementations, so the definition the GPU tests compare with cannot drift.
 Every 16-bit pattern with 64 partners each (half of them near in exponent):
 4.2 M pairs per type. bfloat16: torch's CPU bfloat16 + and *; half: numpy's
 native float16 + and *. Non-NaN results must agree bit for bit, NaN-ness
-everywhere; the model's NaNs are canonical.
+everywhere; the model's NaNs are canonical. The same on product_pairs (every
+pattern with 64 partners aimed at the product's edges), and the properties of
+both sets that tests/test_gpu_half_pairs.py relies on.
 """
 import os
 import subprocess
@@ -28,9 +30,9 @@ def torch_bf16(tmp_path_factory):
     return np.load(out)
 
 
-def native(dtype, op, a, b, torch_bf16):
+def native(dtype, op, pairs, a, b, torch_bf16):
     if dtype == "bfloat16":
-        return torch_bf16[op]
+        return torch_bf16[f"{pairs}_{op}"]
     with np.errstate(all="ignore"):
         x, y = a.view(np.float16), b.view(np.float16)
         return (x + y if op == "sum" else x * y).view(np.uint16)
@@ -43,9 +45,21 @@ def is_nan(dtype, bits):
 @pytest.mark.parametrize("dtype", R.TYPES)
 @pytest.mark.parametrize("op", ["sum", "prod"])
 def test_model_equals_native_arithmetic(dtype, op, torch_bf16):
-    a, b = R.exhaustive_pairs(dtype)
+    model_equals_native(dtype, op, "exhaustive", torch_bf16)
+
+
+@pytest.mark.parametrize("dtype", R.TYPES)
+@pytest.mark.parametrize("op", ["sum", "prod"])
+def test_model_equals_native_arithmetic_on_product_pairs(dtype, op, torch_bf16):
+    """the same on the product-edge set: subnormal, underflowing and
+    overflowing results are where a rounding model goes wrong"""
+    model_equals_native(dtype, op, "product", torch_bf16)
+
+
+def model_equals_native(dtype, op, pairs, torch_bf16):
+    a, b = R.PAIR_SETS[pairs](dtype)
     got = R.step(op, dtype, a, b)
-    want = native(dtype, op, a, b, torch_bf16)
+    want = native(dtype, op, pairs, a, b, torch_bf16)
     nan_g, nan_w = is_nan(dtype, got), is_nan(dtype, want)
     assert (nan_g == nan_w).all()
     assert (got[nan_g] == R.CANONICAL_NAN[dtype]).all()
@@ -117,6 +131,49 @@ def test_fold_order_and_inputs(dtype):
         assert (R.fold("sum", dtype, srcs, q) == want).all()
     # per-step rounding makes the members' sums differ somewhere
     assert (R.fold("sum", dtype, srcs, 0) != R.fold("sum", dtype, srcs, 2)).any()
+
+
+@pytest.mark.parametrize("dtype", R.TYPES)
+def test_product_pairs_reach_the_products_edges(dtype):
+    """conditions on the inputs, from the model alone: among the pairs with
+    both operands finite and non-zero, the shares of products that are
+    subnormal, zero, infinite and in the top two finite binades"""
+    mant, emax_field = (10, 31) if dtype == "half" else (7, 255)
+    a, b = R.product_pairs(dtype)
+    ea, eb = (a & 0x7FFF) >> mant, (b & 0x7FFF) >> mant
+    proper = (ea < emax_field) & (eb < emax_field) & (a & 0x7FFF != 0) & (b & 0x7FFF != 0)
+    r = R.step("prod", dtype, a, b)[proper] & 0x7FFF
+    er = r >> mant
+    share = {"subnormal": ((er == 0) & (r != 0)).mean(), "zero": (r == 0).mean(),
+             "infinite": (r == emax_field << mant).mean(), "top two binades": ((er == emax_field - 1) | (er == emax_field - 2)).mean()}
+    print(dtype, {k: round(float(v), 4) for k, v in share.items()})
+    assert not np.isnan(R.widen(dtype, r)).any()    # finite non-zero operands make no NaN
+    assert share["subnormal"] >= 0.10, share
+    assert share["zero"] >= 0.01, share
+    assert share["infinite"] >= 0.05, share
+    assert share["top two binades"] >= 0.04, share
+
+
+@pytest.mark.parametrize("dtype", R.TYPES)
+def test_pair_sets_hold_every_pattern_and_order_sensitive_chains(dtype):
+    every = np.arange(1 << 16, dtype=np.uint16)
+    for pairs in R.PAIR_SETS.values():
+        a, b = pairs(dtype)
+        assert a.size == b.size == 64 << 16 and a.dtype == b.dtype == np.uint16
+        assert (a.reshape(1 << 16, 64) == every[:, None]).all()     # every pattern, 64 partners each
+    # the 9-source subset: every 8th pair still holds every pattern as a, with 8 partners
+    assert (a[::8].reshape(1 << 16, 8) == every[:, None]).all()
+    a, b = R.exhaustive_pairs(dtype)
+    c = R.third_operand(dtype, a, b)
+    mant = 10 if dtype == "half" else 7
+    es, ec = (R.step("sum", dtype, a, b) & 0x7FFF) >> mant, (c & 0x7FFF) >> mant
+    assert (np.abs(es.astype(np.int64) - ec)[1::2] <= 3).all()
+    assert np.isin(c[::64], R.special_table(dtype)).all() and not np.isfinite(R.widen(dtype, c[::64])).any()
+    assert (R.third_operand(dtype, a, b, 1) != c).mean() > 0.9      # another seed, another array
+    # per-step rounding makes the members' sums differ: an order mistake cannot pass
+    srcs = [a, b, c]
+    assert (R.fold("sum", dtype, srcs, 0) != R.fold("sum", dtype, srcs, 2)).sum() >= 1000
+    assert (R.fold("min", dtype, srcs[:2], 0) != R.fold("min", dtype, srcs[:2], 1)).sum() >= 1000
 
 
 def test_bf16_helpers_equal_the_model():
