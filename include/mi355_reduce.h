@@ -152,6 +152,42 @@ int mi355_strided_pull (int elem_size, void *const *dsts, const void *const *src
 int mi355_strided_copy (int elem_size, void *const *dsts, const void *const *srcs,
                         ptrdiff_t dst_stride, ptrdiff_t src_stride, size_t nelems, int nseg, void *stream);
 
+/* ---- remote atomics (amo.hip; shmem_<T>_swap / cswap / fadd / fetch / set,
+ *      shmemx_<T>_atomic_add_v) ---------------------------------------------- */
+enum mi355_amo_op {
+    MI355_AMO_SWAP = 0,   /* *target = value                           old value out */
+    MI355_AMO_CSWAP = 1,  /* if (*target == cond) *target = value      old value out */
+    MI355_AMO_FADD = 2,   /* *target += value (unsigned, wraps)        old value out */
+    MI355_AMO_FETCH = 3,  /* nothing                                   the value out */
+    MI355_AMO_SET = 4,    /* *target = value                           nothing out   */
+    MI355_NUM_AMO_OPS = 5
+};
+
+/* One atomic operation of `width` 4 or 8 bytes on *target (this GPU's memory
+ * or a peer's mapped here; width-aligned) at system scope, by one lane of a
+ * one-wave kernel. value and cond carry the operands' bit patterns in their
+ * low `width` bytes: the kernel works on unsigned integers and never sees a
+ * floating type. The old value goes, zero-extended, to *result_slot (8 bytes
+ * of device-visible host-coherent memory; may be NULL), stored at system
+ * scope BEFORE the launch's completion signal, so a host that has seen the
+ * signal (or synchronized the stream) reads it. The kernel waits for nothing. */
+int mi355_amo (int op, int width, void *target, unsigned long long value, unsigned long long cond,
+               unsigned long long *result_slot, void *stream);
+
+/* target[i] += source[i] atomically for i < n: no-return atomic adds at system
+ * scope, lane-consecutive elements (one dword or qword per lane, 256 or 512
+ * contiguous bytes per wave-instruction), grid-stride. dtype: MI355_INT,
+ * MI355_LONG, MI355_LONGLONG (wrapping), MI355_FLOAT, MI355_DOUBLE. Both
+ * pointers element-aligned, nothing more; the source is only read. Several
+ * callers may add into one target at once; a float or double sum then
+ * depends on the arrival order in its last bits. */
+int mi355_atomic_add_v (int dtype, void *target, const void *source, size_t n, void *stream);
+
+/* The grid mi355_atomic_add_v launches for n elements on a GPU of `cus`
+ * compute units, and the elements one pass of that grid covers (amo_plan.h;
+ * host-only arithmetic). n == 0: no launch, 0 and 0. Either output may be NULL. */
+void mi355_atomic_add_v_plan (size_t n, int cus, unsigned *grid, unsigned long long *pass);
+
 /* The two-member all-gather of a float/double sum or product: dst[i] =
  * own[i] quieted where own[i] is a NaN, else peer[i] (the other member's shard,
  * folded in its order: the same bits as this member's order except where

@@ -27,6 +27,58 @@ void pshmem_barrier_all (void);
 void pshmem_barrier (int PE_start, int logPE_stride, int PE_size, long *pSync);
 void pshmem_quiet (void);
 
+void pshmem_fence (void);
+
+    void pshmem_short_wait_until (volatile short *ivar, int cmp,
+                                  short cmp_value);
+    void pshmem_int_wait_until (volatile int *ivar, int cmp, int cmp_value);
+    void pshmem_long_wait_until (volatile long *ivar, int cmp, long cmp_value);
+    void pshmem_longlong_wait_until (volatile long long *ivar, int cmp,
+                                            long long cmp_value);
+    void pshmem_short_wait (volatile short *ivar, short cmp_value);
+    void pshmem_int_wait (volatile int *ivar, int cmp_value);
+    void pshmem_long_wait (volatile long *ivar, long cmp_value);
+    void pshmem_longlong_wait (volatile long long *ivar, long long cmp_value);
+    int pshmem_int_swap (int *target, int value, int pe) _WUR;
+    long pshmem_long_swap (long *target, long value, int pe) _WUR;
+    long long pshmem_longlong_swap (long long *target, long long value,
+                                           int pe) _WUR;
+    float pshmem_float_swap (float *target, float value, int pe) _WUR;
+    double pshmem_double_swap (double *target, double value,
+                                      int pe) _WUR;
+    int pshmem_int_cswap (int *target, int cond, int value, int pe) _WUR;
+    long pshmem_long_cswap (long *target, long cond, long value,
+                                   int pe) _WUR;
+    long long pshmem_longlong_cswap (long long *target, long long cond,
+                                            long long value, int pe) _WUR;
+    int pshmem_int_fadd (int *target, int value, int pe) _WUR;
+    long pshmem_long_fadd (long *target, long value, int pe) _WUR;
+    long long pshmem_longlong_fadd (long long *target, long long value,
+                                           int pe) _WUR;
+    int pshmem_int_finc (int *target, int pe) _WUR;
+    long pshmem_long_finc (long *target, int pe) _WUR;
+    long long pshmem_longlong_finc (long long *target, int pe) _WUR;
+    void pshmem_int_add (int *target, int value, int pe);
+    void pshmem_long_add (long *target, long value, int pe);
+    void pshmem_longlong_add (long long *target, long long value,
+                                     int pe);
+    void pshmem_int_inc (int *target, int pe);
+    void pshmem_long_inc (long *target, int pe);
+    void pshmem_longlong_inc (long long *target, int pe);
+    void pshmem_set_lock (volatile long *lock);
+    void pshmem_clear_lock (volatile long *lock);
+    int  pshmem_test_lock (volatile long *lock) _WUR;
+    int pshmem_int_fetch (const int *target, int pe);
+    long pshmem_long_fetch (const long *target, int pe);
+    long long pshmem_longlong_fetch (const long long *target, int pe);
+    float pshmem_float_fetch (const float *target, int pe);
+    double pshmem_double_fetch (const double *target, int pe);
+    void pshmem_int_set (int *target, int value, int pe);
+    void pshmem_long_set (long *target, long value, int pe);
+    void pshmem_longlong_set (long long *target, long long value, int pe);
+    void pshmem_float_set (float *target, float value, int pe);
+    void pshmem_double_set (double *target, double value, int pe);
+
 void pshmem_putmem (void *dest, const void *src, size_t nelems, int pe);
 void pshmem_getmem (void *dest, const void *src, size_t nelems, int pe);
 void pshmem_put32 (void *dest, const void *src, size_t nelems, int pe);

@@ -28,6 +28,17 @@
 # define COMPLEXIFY(T) T _Complex
 #endif
 
+/* results that must not be dropped (reference src/shmem.h:94-102) */
+#if defined(__GNUC__)                                                   \
+    || defined(__PGIC__)                                                \
+    || defined(__INTEL_COMPILER)                                        \
+    || defined(__OPEN64__)                                              \
+    || defined(__OPENUH__)
+# define _WUR __attribute__((__warn_unused_result__))
+#else
+# define _WUR
+#endif
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -159,6 +170,80 @@ long long shmem_longlong_g (long long *addr, int pe);
 float shmem_float_g (float *addr, int pe);
 double shmem_double_g (double *addr, int pe);
 long double shmem_longdouble_g (long double *addr, int pe);
+
+/* ---- ordering (reference src/shmem.h:759-797): every put and atomic of this
+ *      build is complete at its target once the library stream has drained,
+ *      so shmem_fence is shmem_quiet ---- */
+void shmem_fence (void);
+
+/* ---- point-to-point synchronisation (reference src/shmem.h:1044-1123): wait
+ *      until this PE's copy of a symmetric variable, in either symmetric
+ *      heap, compares true against cmp_value (shmem_wait: until it differs).
+ *      A host loop, bounded by SHMEM_WAIT_TIMEOUT ---- */
+    enum shmem_cmp_constants
+        {
+            SHMEM_CMP_EQ = 0,
+            SHMEM_CMP_NE,
+            SHMEM_CMP_GT,
+            SHMEM_CMP_LE,
+            SHMEM_CMP_LT,
+            SHMEM_CMP_GE
+        };
+    void shmem_long_wait_until (volatile long *ivar, int cmp, long cmp_value);
+    void shmem_short_wait_until (volatile short *ivar, int cmp,
+                                 short cmp_value);
+    void shmem_int_wait_until (volatile int *ivar, int cmp, int cmp_value);
+    void shmem_longlong_wait_until (volatile long long *ivar, int cmp,
+                                    long long cmp_value);
+    void shmem_long_wait (volatile long *ivar, long cmp_value);
+    void shmem_short_wait (volatile short *ivar, short cmp_value);
+    void shmem_int_wait (volatile int *ivar, int cmp_value);
+    void shmem_longlong_wait (volatile long long *ivar, long long cmp_value);
+
+/* ---- atomics (reference src/shmem.h:1126-1314, :1899-2027): the target in the
+ *      device symmetric heap or the symmetric host heap; complete at the
+ *      target on return. Integer arithmetic wraps; the float and double forms
+ *      move bit patterns ---- */
+    long shmem_long_swap (long *target, long value, int pe) _WUR;
+    int shmem_int_swap (int *target, int value, int pe) _WUR;
+    long long shmem_longlong_swap (long long *target, long long value,
+                                   int pe) _WUR;
+    float shmem_float_swap (float *target, float value, int pe) _WUR;
+    double shmem_double_swap (double *target, double value, int pe) _WUR;
+    long shmem_long_cswap (long *target, long cond, long value,
+                           int pe) _WUR;
+    int shmem_int_cswap (int *target, int cond, int value, int pe) _WUR;
+    long long shmem_longlong_cswap (long long *target, long long cond,
+                                    long long value, int pe) _WUR;
+    long shmem_long_fadd (long *target, long value, int pe) _WUR;
+    int shmem_int_fadd (int *target, int value, int pe) _WUR;
+    long long shmem_longlong_fadd (long long *target, long long value,
+                                   int pe) _WUR;
+    long shmem_long_finc (long *target, int pe) _WUR;
+    int shmem_int_finc (int *target, int pe) _WUR;
+    long long shmem_longlong_finc (long long *target, int pe) _WUR;
+    void shmem_long_add (long *target, long value, int pe);
+    void shmem_int_add (int *target, int value, int pe);
+    void shmem_longlong_add (long long *target, long long value, int pe);
+    void shmem_long_inc (long *target, int pe);
+    void shmem_int_inc (int *target, int pe);
+    void shmem_longlong_inc (long long *target, int pe);
+    int shmem_int_fetch (const int *dest, int pe);
+    long shmem_long_fetch (const long *dest, int pe);
+    long long shmem_longlong_fetch (const long long *dest, int pe);
+    float shmem_float_fetch (const float *dest, int pe);
+    double shmem_double_fetch (const double *dest, int pe);
+    void shmem_int_set (int *dest, int value, int pe);
+    void shmem_long_set (long *dest, long value, int pe);
+    void shmem_longlong_set (long long *dest, long long value, int pe);
+    void shmem_float_set (float *dest, float value, int pe);
+    void shmem_double_set (double *dest, double value, int pe);
+
+/* ---- locks (reference src/shmem.h:1808-1896): a symmetric long that starts
+ *      at 0; shmem_test_lock returns 0 when it took the lock and never blocks ---- */
+    void shmem_set_lock (volatile long *lock);
+    void shmem_clear_lock (volatile long *lock);
+    int shmem_test_lock (volatile long *lock) _WUR;
 
 /* ---- broadcast / collect (reference src/shmem.h:1746-1779); sources in the
  *      device symmetric heap ---- */
@@ -326,6 +411,94 @@ void shmem_alltoalls64 (void *target, const void *source, ptrdiff_t dst, ptrdiff
     void shmem_longdouble_min_to_all (long double *target, long double *source,
             int nreduce, int PE_start, int logPE_stride, int PE_size,
             long double *pWrk, long *pSync);
+
+/* ---- C11 generic selection over the atomics and waits (reference
+ *      src/shmem.h:2112-2201) ---- */
+#ifdef __STDC_VERSION__
+#if  __STDC_VERSION__ >= 201112L
+
+#define shmem_swap(dest, value, pe)                             \
+    _Generic(*(dest),                                           \
+             int:          shmem_int_swap,                      \
+             long:         shmem_long_swap,                     \
+             long long:    shmem_longlong_swap,                 \
+             float:        shmem_float_swap,                    \
+             double:       shmem_double_swap) (dest, value, pe)
+
+#define shmem_cswap(dest, cond, value, pe)                              \
+    _Generic(*(dest),                                                   \
+             int:          shmem_int_cswap,                             \
+             long:         shmem_long_cswap,                            \
+             long long:    shmem_longlong_cswap) (dest, cond, value, pe)
+
+#define shmem_fadd(dest, value, pe)                                 \
+    _Generic(*(dest),                                               \
+             int:          shmem_int_fadd,                          \
+             long:         shmem_long_fadd,                         \
+             long long:    shmem_longlong_fadd) (dest, value, pe)
+
+#define shmem_finc(dest, pe)                                \
+    _Generic(*(dest),                                       \
+             int:          shmem_int_finc,                  \
+             long:         shmem_long_finc,                 \
+             long long:    shmem_longlong_finc) (dest, pe)
+
+#define shmem_add(dest, value, pe)                                  \
+    _Generic(*(dest),                                               \
+             int:          shmem_int_add,                           \
+             long:         shmem_long_add,                          \
+             long long:    shmem_longlong_add) (dest, value, pe)
+
+#define shmem_inc(dest, pe)                                 \
+    _Generic(*(dest),                                       \
+             int:          shmem_int_inc,                   \
+             long:         shmem_long_inc,                  \
+             long long:    shmem_longlong_inc) (dest, pe)
+
+#define shmem_fetch(dest, pe)                               \
+    _Generic(*(dest),                                       \
+             int:          shmem_int_fetch,                 \
+             const int:    shmem_int_fetch,                 \
+             long:         shmem_long_fetch,                \
+             const long:   shmem_long_fetch,                \
+             long long:    shmem_longlong_fetch,            \
+             const long long: shmem_longlong_fetch,         \
+             float:        shmem_float_fetch,               \
+             const float:  shmem_float_fetch,               \
+             double:       shmem_double_fetch,              \
+             const double: shmem_double_fetch) (dest, pe)
+
+#define shmem_set(dest, value, pe)                              \
+    _Generic(*(dest),                                           \
+             int:          shmem_int_set,                       \
+             long:         shmem_long_set,                      \
+             long long:    shmem_longlong_set,                  \
+             float:        shmem_float_set,                     \
+             double:       shmem_double_set) (dest, value, pe)
+
+#define shmem_wait(ivar, cmp_value)                                 \
+    _Generic(*(ivar),                                               \
+             short:        shmem_short_wait,                        \
+             int:          shmem_int_wait,                          \
+             long:         shmem_long_wait,                         \
+             long long:    shmem_longlong_wait) (ivar, cmp_value)
+
+#define shmem_wait_until(ivar, cmp, cmp_value)                          \
+    _Generic(*(ivar),                                                   \
+             short:        shmem_short_wait_until,                      \
+             int:          shmem_int_wait_until,                        \
+             long:         shmem_long_wait_until,                       \
+             long long:    shmem_longlong_wait_until) (ivar, cmp, cmp_value)
+
+#endif   /* __STDC_VERSION__ >= 201112L test */
+#endif /* __STDC_VERSION__ defined test */
+
+#define _SHMEM_CMP_EQ                   SHMEM_CMP_EQ
+#define _SHMEM_CMP_NE                   SHMEM_CMP_NE
+#define _SHMEM_CMP_GT                   SHMEM_CMP_GT
+#define _SHMEM_CMP_LE                   SHMEM_CMP_LE
+#define _SHMEM_CMP_LT                   SHMEM_CMP_LT
+#define _SHMEM_CMP_GE                   SHMEM_CMP_GE
 
 #ifdef __cplusplus
 }

@@ -143,6 +143,42 @@ void shmem_iget8_ (void *target, const void *source, int *tst, int *sst, int *ne
 void shmem_iget32_ (void *target, const void *source, int *tst, int *sst, int *nelems, int *pe);
 void shmem_iget64_ (void *target, const void *source, int *tst, int *sst, int *nelems, int *pe);
 void shmem_iget128_ (void *target, const void *source, int *tst, int *sst, int *nelems, int *pe);
+/* atomics, waits, locks, fence (reference src/fortran/fortran.c:630-645, :648-938,
+ * :1324-1353): int4 int, int8 long, real4 float, real8 double; the untyped names
+ * act on default INTEGERs */
+void shmem_fence_ (void);
+void shmem_int4_wait_until_ (int *ivar, int *cmp, int *cmp_value);
+void shmem_int8_wait_until_ (long *ivar, int *cmp, long *cmp_value);
+void shmem_wait_until_ (int *ivar, int *cmp, int *cmp_value);
+void shmem_int4_wait_ (int *ivar, int *cmp_value);
+void shmem_int8_wait_ (long *ivar, long *cmp_value);
+void shmem_wait_ (int *ivar, int *cmp_value);
+void shmem_int4_inc_ (int *target, int *pe);
+void shmem_int8_inc_ (long *target, int *pe);
+int shmem_int4_finc_ (int *target, int *pe);
+long shmem_int8_finc_ (long *target, int *pe);
+void shmem_int4_add_ (int *target, int *value, int *pe);
+void shmem_int8_add_ (long *target, long *value, int *pe);
+int shmem_int4_fadd_ (int *target, int *value, int *pe);
+long shmem_int8_fadd_ (long *target, long *value, int *pe);
+int shmem_int4_swap_ (int *target, int *value, int *pe);
+long shmem_int8_swap_ (long *target, long *value, int *pe);
+float shmem_real4_swap_ (float *target, float *value, int *pe);
+double shmem_real8_swap_ (double *target, double *value, int *pe);
+int shmem_swap_ (int *target, int *value, int *pe);
+int shmem_int4_cswap_ (int *target, int *cond, int *value, int *pe);
+long shmem_int8_cswap_ (long *target, long *cond, long *value, int *pe);
+int shmem_int4_fetch_ (int *target, int *pe);
+long shmem_int8_fetch_ (long *target, int *pe);
+float shmem_real4_fetch_ (float *target, int *pe);
+double shmem_real8_fetch_ (double *target, int *pe);
+void shmem_int4_set_ (int *target, int *val, int *pe);
+void shmem_int8_set_ (long *target, long *val, int *pe);
+void shmem_real4_set_ (float *target, float *val, int *pe);
+void shmem_real8_set_ (double *target, double *val, int *pe);
+void shmem_clear_lock_ (long *lock);
+void shmem_set_lock_ (long *lock);
+int shmem_test_lock_ (long *lock);
 
 /* strong (PSHMEM) names */
 void pstart_pes_ (int *npes);
@@ -261,6 +297,39 @@ void pshmem_iget8_ (void *target, const void *source, int *tst, int *sst, int *n
 void pshmem_iget32_ (void *target, const void *source, int *tst, int *sst, int *nelems, int *pe);
 void pshmem_iget64_ (void *target, const void *source, int *tst, int *sst, int *nelems, int *pe);
 void pshmem_iget128_ (void *target, const void *source, int *tst, int *sst, int *nelems, int *pe);
+void pshmem_fence_ (void);
+void pshmem_int4_wait_until_ (int *ivar, int *cmp, int *cmp_value);
+void pshmem_int8_wait_until_ (long *ivar, int *cmp, long *cmp_value);
+void pshmem_wait_until_ (int *ivar, int *cmp, int *cmp_value);
+void pshmem_int4_wait_ (int *ivar, int *cmp_value);
+void pshmem_int8_wait_ (long *ivar, long *cmp_value);
+void pshmem_wait_ (int *ivar, int *cmp_value);
+void pshmem_int4_inc_ (int *target, int *pe);
+void pshmem_int8_inc_ (long *target, int *pe);
+int pshmem_int4_finc_ (int *target, int *pe);
+long pshmem_int8_finc_ (long *target, int *pe);
+void pshmem_int4_add_ (int *target, int *value, int *pe);
+void pshmem_int8_add_ (long *target, long *value, int *pe);
+int pshmem_int4_fadd_ (int *target, int *value, int *pe);
+long pshmem_int8_fadd_ (long *target, long *value, int *pe);
+int pshmem_int4_swap_ (int *target, int *value, int *pe);
+long pshmem_int8_swap_ (long *target, long *value, int *pe);
+float pshmem_real4_swap_ (float *target, float *value, int *pe);
+double pshmem_real8_swap_ (double *target, double *value, int *pe);
+int pshmem_swap_ (int *target, int *value, int *pe);
+int pshmem_int4_cswap_ (int *target, int *cond, int *value, int *pe);
+long pshmem_int8_cswap_ (long *target, long *cond, long *value, int *pe);
+int pshmem_int4_fetch_ (int *target, int *pe);
+long pshmem_int8_fetch_ (long *target, int *pe);
+float pshmem_real4_fetch_ (float *target, int *pe);
+double pshmem_real8_fetch_ (double *target, int *pe);
+void pshmem_int4_set_ (int *target, int *val, int *pe);
+void pshmem_int8_set_ (long *target, long *val, int *pe);
+void pshmem_real4_set_ (float *target, float *val, int *pe);
+void pshmem_real8_set_ (double *target, double *val, int *pe);
+void pshmem_clear_lock_ (long *lock);
+void pshmem_set_lock_ (long *lock);
+int pshmem_test_lock_ (long *lock);
 #ifdef __cplusplus
 }
 #endif

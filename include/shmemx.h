@@ -796,6 +796,23 @@ void shmemx_bfloat16_min_exscan (shmemx_bfloat16_t *target, shmemx_bfloat16_t *s
         int nreduce, int PE_start, int logPE_stride, int PE_size,
         shmemx_bfloat16_t *pWrk, long *pSync);
 
+/* ---- atomic accumulate: target_on_pe[i] += source[i] atomically, i < nelems.
+ *      The one-sided sibling of a sum reduction (MPI_Accumulate, a scatter-add
+ *      into a peer's buffer): several PEs may add into one target at once, and
+ *      the same target may take shmem_<T>_add / fadd meanwhile. The target is
+ *      symmetric, in the device heap (one launch of the accumulate kernel,
+ *      mi355_atomic_add_v, on the peer's mapped heap; the source may be device
+ *      memory or any host memory, which is staged through device scratch) or
+ *      in the host heap (a host loop of atomic adds; for float and double a
+ *      compare-and-swap on the bit pattern). Integers wrap. A float or double
+ *      sum depends on the arrival order in its last bits when several PEs add
+ *      at once. Blocking: complete at the target on return. Not collective. ---- */
+void shmemx_int_atomic_add_v (int *target, const int *source, size_t nelems, int pe);
+void shmemx_long_atomic_add_v (long *target, const long *source, size_t nelems, int pe);
+void shmemx_longlong_atomic_add_v (long long *target, const long long *source, size_t nelems, int pe);
+void shmemx_float_atomic_add_v (float *target, const float *source, size_t nelems, int pe);
+void shmemx_double_atomic_add_v (double *target, const double *source, size_t nelems, int pe);
+
 #ifdef __cplusplus
 }
 #endif

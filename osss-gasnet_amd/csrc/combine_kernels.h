@@ -613,9 +613,10 @@ inline void fire_on_host(hipStream_t st) {
     sig = Signal{nullptr, nullptr, 0};
 }
 
-// `final`: the last launch of an API call, the one that carries the signal
+// `final`: the last launch of an API call, the one that carries the signal;
+// `block`: threads per block (amo.hip's one-wave kernel: 64)
 template <typename K, typename P>
-int launch(K kernel, dim3 grid, hipStream_t st, P p, bool final = true) {
+int launch(K kernel, dim3 grid, hipStream_t st, P p, bool final = true, unsigned block = kBlock) {
     LaunchState &s = t_launch;
     p.sig = Signal{nullptr, nullptr, 0};
     if (final) {
@@ -625,10 +626,10 @@ int launch(K kernel, dim3 grid, hipStream_t st, P p, bool final = true) {
     s.last_kernel = (const void *)kernel;
     s.last_grid[0] = grid.x, s.last_grid[1] = grid.y;
     if (s.ev_start != nullptr || s.ev_stop != nullptr) {
-        hipExtLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, st, s.ev_start, s.ev_stop, 0, p);
+        hipExtLaunchKernelGGL(kernel, grid, dim3(block), 0, st, s.ev_start, s.ev_stop, 0, p);
         s.ev_start = s.ev_stop = nullptr;
     } else {
-        hipLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, st, p);
+        hipLaunchKernelGGL(kernel, grid, dim3(block), 0, st, p);
     }
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : (int)e;

@@ -163,3 +163,75 @@ void shmem_alltoalls64_ (void *target, const void *source, ptrdiff_t *dst, ptrdi
     void Fname (Ctype *target, const Ctype *source, int *tst, int *sst, int *nelems, int *pe) WEAK_F (Fname);
 
 F_STRIDED_ALL (F_STRIDED)
+
+/* ---- atomics, waits, locks, fence (reference src/fortran/fortran.c:630-645,
+ *      :648-938, :1324-1353): int4 -> int, int8 -> long, real4 -> float, real8 ->
+ *      double; the untyped shmem_wait_, shmem_wait_until_ and shmem_swap_ act on
+ *      default INTEGERs, as there ----------------------------------------- */
+
+void pshmem_fence_ (void) { pshmem_fence (); }
+void pshmem_int4_wait_until_ (int *ivar, int *cmp, int *cmp_value) { pshmem_int_wait_until (ivar, *cmp, *cmp_value); }
+void pshmem_int8_wait_until_ (long *ivar, int *cmp, long *cmp_value) { pshmem_long_wait_until (ivar, *cmp, *cmp_value); }
+void pshmem_wait_until_ (int *ivar, int *cmp, int *cmp_value) { pshmem_int_wait_until (ivar, *cmp, *cmp_value); }
+void pshmem_int4_wait_ (int *ivar, int *cmp_value) { pshmem_int_wait (ivar, *cmp_value); }
+void pshmem_int8_wait_ (long *ivar, long *cmp_value) { pshmem_long_wait (ivar, *cmp_value); }
+void pshmem_wait_ (int *ivar, int *cmp_value) { pshmem_int_wait (ivar, *cmp_value); }
+void pshmem_int4_inc_ (int *target, int *pe) { pshmem_int_inc (target, *pe); }
+void pshmem_int8_inc_ (long *target, int *pe) { pshmem_long_inc (target, *pe); }
+int pshmem_int4_finc_ (int *target, int *pe) { return pshmem_int_finc (target, *pe); }
+long pshmem_int8_finc_ (long *target, int *pe) { return pshmem_long_finc (target, *pe); }
+void pshmem_int4_add_ (int *target, int *value, int *pe) { pshmem_int_add (target, *value, *pe); }
+void pshmem_int8_add_ (long *target, long *value, int *pe) { pshmem_long_add (target, *value, *pe); }
+int pshmem_int4_fadd_ (int *target, int *value, int *pe) { return pshmem_int_fadd (target, *value, *pe); }
+long pshmem_int8_fadd_ (long *target, long *value, int *pe) { return pshmem_long_fadd (target, *value, *pe); }
+int pshmem_int4_swap_ (int *target, int *value, int *pe) { return pshmem_int_swap (target, *value, *pe); }
+long pshmem_int8_swap_ (long *target, long *value, int *pe) { return pshmem_long_swap (target, *value, *pe); }
+float pshmem_real4_swap_ (float *target, float *value, int *pe) { return pshmem_float_swap (target, *value, *pe); }
+double pshmem_real8_swap_ (double *target, double *value, int *pe) { return pshmem_double_swap (target, *value, *pe); }
+int pshmem_swap_ (int *target, int *value, int *pe) { return pshmem_int_swap (target, *value, *pe); }
+int pshmem_int4_cswap_ (int *target, int *cond, int *value, int *pe) { return pshmem_int_cswap (target, *cond, *value, *pe); }
+long pshmem_int8_cswap_ (long *target, long *cond, long *value, int *pe) { return pshmem_long_cswap (target, *cond, *value, *pe); }
+int pshmem_int4_fetch_ (int *target, int *pe) { return pshmem_int_fetch (target, *pe); }
+long pshmem_int8_fetch_ (long *target, int *pe) { return pshmem_long_fetch (target, *pe); }
+float pshmem_real4_fetch_ (float *target, int *pe) { return pshmem_float_fetch (target, *pe); }
+double pshmem_real8_fetch_ (double *target, int *pe) { return pshmem_double_fetch (target, *pe); }
+void pshmem_int4_set_ (int *target, int *val, int *pe) { pshmem_int_set (target, *val, *pe); }
+void pshmem_int8_set_ (long *target, long *val, int *pe) { pshmem_long_set (target, *val, *pe); }
+void pshmem_real4_set_ (float *target, float *val, int *pe) { pshmem_float_set (target, *val, *pe); }
+void pshmem_real8_set_ (double *target, double *val, int *pe) { pshmem_double_set (target, *val, *pe); }
+void pshmem_clear_lock_ (long *lock) { pshmem_clear_lock (lock); }
+void pshmem_set_lock_ (long *lock) { pshmem_set_lock (lock); }
+int pshmem_test_lock_ (long *lock) { return pshmem_test_lock (lock); }
+void shmem_fence_ (void) WEAK_F (shmem_fence_);
+void shmem_int4_wait_until_ (int *ivar, int *cmp, int *cmp_value) WEAK_F (shmem_int4_wait_until_);
+void shmem_int8_wait_until_ (long *ivar, int *cmp, long *cmp_value) WEAK_F (shmem_int8_wait_until_);
+void shmem_wait_until_ (int *ivar, int *cmp, int *cmp_value) WEAK_F (shmem_wait_until_);
+void shmem_int4_wait_ (int *ivar, int *cmp_value) WEAK_F (shmem_int4_wait_);
+void shmem_int8_wait_ (long *ivar, long *cmp_value) WEAK_F (shmem_int8_wait_);
+void shmem_wait_ (int *ivar, int *cmp_value) WEAK_F (shmem_wait_);
+void shmem_int4_inc_ (int *target, int *pe) WEAK_F (shmem_int4_inc_);
+void shmem_int8_inc_ (long *target, int *pe) WEAK_F (shmem_int8_inc_);
+int shmem_int4_finc_ (int *target, int *pe) WEAK_F (shmem_int4_finc_);
+long shmem_int8_finc_ (long *target, int *pe) WEAK_F (shmem_int8_finc_);
+void shmem_int4_add_ (int *target, int *value, int *pe) WEAK_F (shmem_int4_add_);
+void shmem_int8_add_ (long *target, long *value, int *pe) WEAK_F (shmem_int8_add_);
+int shmem_int4_fadd_ (int *target, int *value, int *pe) WEAK_F (shmem_int4_fadd_);
+long shmem_int8_fadd_ (long *target, long *value, int *pe) WEAK_F (shmem_int8_fadd_);
+int shmem_int4_swap_ (int *target, int *value, int *pe) WEAK_F (shmem_int4_swap_);
+long shmem_int8_swap_ (long *target, long *value, int *pe) WEAK_F (shmem_int8_swap_);
+float shmem_real4_swap_ (float *target, float *value, int *pe) WEAK_F (shmem_real4_swap_);
+double shmem_real8_swap_ (double *target, double *value, int *pe) WEAK_F (shmem_real8_swap_);
+int shmem_swap_ (int *target, int *value, int *pe) WEAK_F (shmem_swap_);
+int shmem_int4_cswap_ (int *target, int *cond, int *value, int *pe) WEAK_F (shmem_int4_cswap_);
+long shmem_int8_cswap_ (long *target, long *cond, long *value, int *pe) WEAK_F (shmem_int8_cswap_);
+int shmem_int4_fetch_ (int *target, int *pe) WEAK_F (shmem_int4_fetch_);
+long shmem_int8_fetch_ (long *target, int *pe) WEAK_F (shmem_int8_fetch_);
+float shmem_real4_fetch_ (float *target, int *pe) WEAK_F (shmem_real4_fetch_);
+double shmem_real8_fetch_ (double *target, int *pe) WEAK_F (shmem_real8_fetch_);
+void shmem_int4_set_ (int *target, int *val, int *pe) WEAK_F (shmem_int4_set_);
+void shmem_int8_set_ (long *target, long *val, int *pe) WEAK_F (shmem_int8_set_);
+void shmem_real4_set_ (float *target, float *val, int *pe) WEAK_F (shmem_real4_set_);
+void shmem_real8_set_ (double *target, double *val, int *pe) WEAK_F (shmem_real8_set_);
+void shmem_clear_lock_ (long *lock) WEAK_F (shmem_clear_lock_);
+void shmem_set_lock_ (long *lock) WEAK_F (shmem_set_lock_);
+int shmem_test_lock_ (long *lock) WEAK_F (shmem_test_lock_);

@@ -204,6 +204,8 @@ static void check_abort (void)
     }
 }
 
+void shmemi_check_abort (void) { check_abort (); }
+
 static void bootstrap_attach (void)
 {
     const int npes = shmemi.npes;
@@ -544,6 +546,8 @@ static void signal_init (void)
     shmemi.sig_flag = (unsigned *) h;
     *shmemi.sig_flag = 0;
     shmemi.stream_err = (unsigned *) ((char *) h + 64); /* own cache line */
+    shmemi.amo_slot = (unsigned long long *) ((char *) h + 32); /* written before the flag, by the same lane */
+    *shmemi.amo_slot = 0;
     *shmemi.stream_err = 0;
     SHMEMI_HIP (hipMalloc (&d, 64));
     SHMEMI_HIP (hipMemset (d, 0, 64));
@@ -1388,6 +1392,8 @@ void pshmem_init (void)
                       shmemi.mype, shmemi.npes);
     shmemi_trace_init ();
     shmemi.barrier_timeout = (double) env_long (to_env, 600);
+    static const char *wt_env[] = {"SHMEM_WAIT_TIMEOUT", NULL};
+    shmemi.wait_timeout = (double) env_long (wt_env, 86400);
     shmemi.debug = (int) env_long (dbg_env, 0);
     static const char *es_env[] = {"SHMEM_ENTRY_SYNC", NULL};
     shmemi.entry_sync = (int) env_long (es_env, 0);

@@ -180,6 +180,8 @@ struct shmemi_state {
     unsigned *sig_flag;         /* hipHostMalloc coherent+mapped, same address on both sides */
     unsigned *sig_count;        /* device word, 0 between launches */
     unsigned sig_epoch;
+    unsigned long long *amo_slot; /* host-coherent, in sig_flag's allocation: mi355_amo's old value (amo.c) */
+    double wait_timeout;        /* SHMEM_WAIT_TIMEOUT, seconds: shmem_wait*, shmem_set_lock (amo.c) */
 
     /* stream-ordered collectives (shmemx_*_on_stream, streamops.c) */
     unsigned *stream_err;       /* host-coherent: a device-side wait timed out */
@@ -256,6 +258,7 @@ void shmemi_order_after_caller (int host_wait);
 void shmemi_check_stream_err (const char *fn);
 void shmemi_peer_acquire (hipStream_t st);
 double shmemi_now (void);
+void shmemi_check_abort (void);
 
 /* hostheap.c: shmem_malloc's symmetric heap in host memory, mapped by every PE */
 void shmemi_hheap_create (size_t size);
@@ -315,7 +318,8 @@ void shmemi_ext_finalize (void);
 enum shmemi_log_level {
     SHMEMI_LOG_DEBUG = 1, SHMEMI_LOG_INFO, SHMEMI_LOG_VERSION, SHMEMI_LOG_INIT, SHMEMI_LOG_FINALIZE,
     SHMEMI_LOG_BARRIER, SHMEMI_LOG_BROADCAST, SHMEMI_LOG_REDUCTION, SHMEMI_LOG_COLLECT, SHMEMI_LOG_QUIET,
-    SHMEMI_LOG_MEMORY, SHMEMI_LOG_NOTICE, SHMEMI_LOG_ALLTOALL, SHMEMI_LOG_NLEVELS
+    SHMEMI_LOG_MEMORY, SHMEMI_LOG_NOTICE, SHMEMI_LOG_ALLTOALL, SHMEMI_LOG_ATOMIC, SHMEMI_LOG_LOCK,
+    SHMEMI_LOG_NLEVELS
 };
 #define SHMEMX_VERSION_STRING "osss-gasnet MI355X reduction path (OpenSHMEM 1.3 API, gfx950)"
 extern unsigned shmemi_trace_mask;

@@ -34,7 +34,8 @@ static const char *const level_names[SHMEMI_LOG_NLEVELS] = {
     [SHMEMI_LOG_BROADCAST] = "BROADCAST", [SHMEMI_LOG_REDUCTION] = "REDUCTION",
     [SHMEMI_LOG_COLLECT] = "COLLECT",     [SHMEMI_LOG_QUIET] = "QUIET",
     [SHMEMI_LOG_MEMORY] = "MEMORY",       [SHMEMI_LOG_NOTICE] = "NOTICE",
-    [SHMEMI_LOG_ALLTOALL] = "ALLTOALL",
+    [SHMEMI_LOG_ALLTOALL] = "ALLTOALL",   [SHMEMI_LOG_ATOMIC] = "ATOMIC",
+    [SHMEMI_LOG_LOCK] = "LOCK",
 };
 
 static double mono_s (void)
@@ -137,6 +138,8 @@ void shmemi_trace_show_info (void)
         {"SHMEM_DEVICE_WAITS", "1: keep device-side waits (fused kernel, device barriers) even where init finds them time-sliced; 0: host barriers"},
         {"SHMEM_ONESHOT_MAX_BYTES", "largest fused message folded one-shot, not reduce-scatter + all-gather (default 64K)"},
         {"SHMEM_BARRIER_TIMEOUT", "seconds before a barrier wait aborts the job (default 600)"},
+        {"SHMEM_WAIT_TIMEOUT", "seconds before shmem_wait / shmem_wait_until / shmem_set_lock abort the job "
+                               "(default 86400)"},
         {"SHMEM_BOOTSTRAP_TIMEOUT", "seconds a PE waits at init for PE 0 to create the job's segment (default: "
                                     "SHMEM_BARRIER_TIMEOUT)"},
         {"SHMEM_DEBUG", "1: check pSync and exchange every collective's arguments between its members, aborting "

@@ -411,6 +411,93 @@ class Shmem:
         source symmetric. Blocking."""
         self._strided_fn("get", elem_size)(target, source, tst, sst, nelems, pe)
 
+    # ---- atomics, waits, locks (include/shmem.h; csrc/atomic.c)
+    _AMO_C = {"short": ctypes.c_short, "int": ctypes.c_int, "long": ctypes.c_long, "longlong": ctypes.c_longlong,
+              "float": ctypes.c_float, "double": ctypes.c_double}
+    _AMO_ARGS = {"swap": "v", "cswap": "cv", "fadd": "v", "finc": "", "add": "v", "inc": "", "fetch": "", "set": "v"}
+    AMO_OPS = ["swap", "cswap", "fadd", "fetch", "set"]                 # enum mi355_amo_op
+    CMP = {"eq": 0, "ne": 1, "gt": 2, "le": 3, "lt": 4, "ge": 5}       # enum shmem_cmp_constants
+
+    def _typed_fn(self, name, restype, argtypes):
+        f = self._fns.get(name)
+        if f is None:
+            f = getattr(self.lib, name)
+            f.restype = restype
+            f.argtypes = argtypes
+            self._fns[name] = f
+        return f
+
+    def atomic(self, op, dtype, ptr, pe, value=None, cond=None):
+        """shmem_<dtype>_<op> on the symmetric object at ptr on PE pe: op one
+        of swap, cswap, fadd, finc, add, inc, fetch, set; dtype int, long,
+        longlong (every op) or float, double (swap, fetch, set). Returns the
+        old value for the fetching ops, None for add, inc and set."""
+        ct = self._AMO_C[dtype]
+        fetching = op not in ("add", "inc", "set")
+        extra = [ct] * len(self._AMO_ARGS[op])
+        f = self._typed_fn(f"shmem_{dtype}_{op}", ct if fetching else None, [_vp] + extra + [_i])
+        args = {"": [], "v": [value], "cv": [cond, value]}[self._AMO_ARGS[op]]
+        if any(a is None for a in args):
+            raise ValueError(f"{op} needs " + ("cond and value" if op == "cswap" else "value"))
+        return f(ptr, *args, pe)
+
+    def wait_until(self, dtype, ptr, cmp, value):
+        """shmem_<dtype>_wait_until: dtype short, int, long or longlong; cmp one of eq ne gt le lt ge"""
+        ct = self._AMO_C[dtype]
+        self._typed_fn(f"shmem_{dtype}_wait_until", None, [_vp, _i, ct])(ptr, self.CMP[cmp], value)
+
+    def set_lock(self, lock):
+        self._typed_fn("shmem_set_lock", None, [_vp])(lock)
+
+    def clear_lock(self, lock):
+        self._typed_fn("shmem_clear_lock", None, [_vp])(lock)
+
+    def test_lock(self, lock):
+        """0 when this PE took the lock, non-zero when it is busy; never blocks"""
+        return self._typed_fn("shmem_test_lock", _i, [_vp])(lock)
+
+    def quiet(self):
+        self._typed_fn("shmem_quiet", None, [])()
+
+    def fence(self):
+        self._typed_fn("shmem_fence", None, [])()
+
+    def atomic_add_v(self, dtype, target, source, nelems, pe):
+        """shmemx_<dtype>_atomic_add_v: target_on_pe[i] += source[i] atomically
+        for i < nelems; dtype int, long, longlong, float or double; target
+        symmetric, source any device or host memory. Blocking."""
+        self._typed_fn(f"shmemx_{dtype}_atomic_add_v", None, [_vp, _vp, _sz, _i])(target, source, nelems, pe)
+
+    def atomic_add_v_tensors(self, target, source, pe):
+        """The same on tensors: `target` a heap_tensor, `source` any contiguous
+        torch tensor (GPU or CPU) of the same dtype and size."""
+        name = TORCH_DTYPES.get(str(target.dtype).replace("torch.", ""))
+        if name not in ("int", "long", "float", "double"):
+            raise TypeError(f"no atomic_add_v for {target.dtype}")
+        if target.dtype != source.dtype or target.numel() != source.numel() or \
+                not (target.is_contiguous() and source.is_contiguous()):
+            raise ValueError("target and source must be contiguous tensors of one dtype and size")
+        self.atomic_add_v(name, target.data_ptr(), source.data_ptr(), target.numel(), pe)
+
+    def amo_raw(self, op, width, target, value=0, cond=0, slot=None, stream=None):
+        """mi355_amo: one atomic of `width` bytes on device-visible memory;
+        op one of AMO_OPS; the old value goes to the 8 bytes at `slot`"""
+        f = self._typed_fn("mi355_amo", _i, [_i, _i, _vp, ctypes.c_ulonglong, ctypes.c_ulonglong, _vp, _vp])
+        return f(self.AMO_OPS.index(op), width, target, value, cond, slot, stream)
+
+    def atomic_add_v_raw(self, dtype, target, source, n, stream=None):
+        """mi355_atomic_add_v: target[i] += source[i] atomically, i < n"""
+        f = self._typed_fn("mi355_atomic_add_v", _i, [_i, _vp, _vp, _sz, _vp])
+        return f(DTYPES.index(dtype), target, source, n, stream)
+
+    def atomic_add_v_plan(self, n, cus):
+        """(grid, elements per grid pass) of mi355_atomic_add_v for n elements on `cus` compute units"""
+        f = self._typed_fn("mi355_atomic_add_v_plan", None,
+                           [_sz, _i, ctypes.POINTER(ctypes.c_uint), ctypes.POINTER(ctypes.c_ulonglong)])
+        g, p = ctypes.c_uint(), ctypes.c_ulonglong()
+        f(n, cus, ctypes.byref(g), ctypes.byref(p))
+        return g.value, p.value
+
     def heap_tensor(self, n, dtype):
         """A 1-D torch tensor of n elements of torch dtype `dtype` in the
         device symmetric heap (collective, like shmemx_malloc_device): the
