@@ -32,6 +32,11 @@
  * Buffers outside the device symmetric heap (host memory from shmem_malloc,
  * static arrays, other device memory) are staged through the heap's scratch
  * area in chunks: copy in, reduce device-resident, copy out.
+ *
+ * Which schedule a call on symmetric heap offsets runs is decided in
+ * sched_plan.h (plan_schedule: host-only, enumerated on the CPU by
+ * tests/test_sched_plan.py); this file fills its request and executes its
+ * plan (run_blocking, reduce_on_stream).
  */
 #define _GNU_SOURCE
 #include <stdio.h>
@@ -43,6 +48,8 @@
 #include "shmem.h"
 #include "shmemx.h"
 #include "shmemi.h"
+#include "prefix_plan.h"
+#include "sched_plan.h"
 
 enum { SHMEMI_CHAN_HOST = 0, SHMEMI_CHAN_STREAM = 1 }; /* signal-region channels */
 
@@ -165,116 +172,67 @@ static void copy_wait (void *const *dsts, const void *const *srcs, const size_t 
     shmemi_wait_signal ();
 }
 
-static int ranges_overlap (size_t a, size_t b, size_t nbytes)
-{
-    return a < b + nbytes && b < a + nbytes;
-}
-
-/* Elements per shard: ceil(n / size) rounded up so every shard starts on a
- * 256-byte boundary. */
-static size_t shard_chunk (size_t n, size_t es, int size)
-{
-    size_t align = es >= 256 ? 1 : 256 / es;
-    size_t chunk = (n + (size_t) size - 1) / (size_t) size;
-    return (chunk + align - 1) / align * align;
-}
-
-/* Shard bounds of member i for n elements of es bytes over `size` members. */
 void mi355_shard_bounds (size_t n, size_t es, int size, int i, size_t *lo, size_t *hi)
 {
-    const size_t chunk = shard_chunk (n, es, size);
-    size_t l = (size_t) i * chunk;
-    *lo = l < n ? l : n;
-    *hi = l + chunk < n ? l + chunk : n;
+    shard_bounds (n, es, size, i, lo, hi);
 }
 
 /* ---------------------------------------------------------------------- */
-/* result order (shmemx.h, SHMEMX_ORDER_REFERENCE)                          */
+/* the planner's two sides (sched_plan.h)                                  */
 /* ---------------------------------------------------------------------- */
-/* The reference's members disagree on this reduction: floating point (the
- * integer and bitwise operators wrap, select identical bits or are exact, so
- * any order gives the same bits), and either 3+ members (the rounding follows
- * the order), min/max (`a < b ? a : b` picks by position when a NaN or a +-0
- * pair is involved, reduce-op.c:138-150, from 2 members on), or a two-member
- * float, double or complex sum/prod: a + b and b + a have the same value, but
- * where both operands are NaNs SSE returns the FIRST one (ops.h x86_result),
- * so the two members' results differ in payload. x87 long double returns the
- * NaN with the larger significand whatever the order (x80.h), so its
- * two-member sum/prod agree. So do half's and bfloat16's (shmemx.h): a NaN
- * out of their sum or prod is the canonical one whatever the operands were. */
-static int order_sensitive (int op, int dtype, int size)
+static int scan_direct_forced (void)
 {
-    if (shmemi.order != SHMEMX_ORDER_REFERENCE || size < 2)
-        return 0;
-    if (dtype != MI355_FLOAT && dtype != MI355_DOUBLE && dtype != MI355_LONGDOUBLE && dtype != MI355_COMPLEXF &&
-        dtype != MI355_COMPLEXD && dtype != MI355_HALF && dtype != MI355_BFLOAT16)
-        return 0;
-    return size > 2 || op == MI355_OP_MIN || op == MI355_OP_MAX ||
-           (dtype != MI355_LONGDOUBLE && dtype != MI355_HALF && dtype != MI355_BFLOAT16);
+    static int forced = -1;
+    if (forced < 0) {
+        const char *e = getenv ("SHMEM_SCAN_DIRECT");
+        forced = e != NULL && atoi (e) != 0;
+    }
+    return forced;
 }
 
-/* The one-launch fused kernel and the persistent server (fused.hip) have no
- * instantiations for the 16-bit float types: their calls take the
- * multi-launch schedules at every size. */
-static int fused_dtype (int dtype)
+/* The job's state as the planner sees it. */
+static struct sched_env sched_env_now (void)
 {
-    return dtype != MI355_HALF && dtype != MI355_BFLOAT16;
+    const struct sched_env e = {shmemi.order, shmemi.algorithm, shmemi.fused_max, shmemi.oneshot_max,
+                                shmemi.order_chunk, shmemi.scratch_chunk, shmemi.npes, shmemi.sigmem != NULL,
+                                shmemi.sig_broken, shmemi.dev_wait_slow, shmemi.p2p_broken, shmemi.srv.enabled,
+                                scan_direct_forced ()};
+    return e;
 }
 
-/* The shard schedules deliver every member's order up to
- * MI355_ORDERS_MAX_SOURCES members (mi355_combine_orders); larger
- * order-sensitive active sets run the EXACT schedule instead. */
-static int ordered_pair (int op, int dtype, int size)
+/* A plan's error (fn: the stream entry point, for its messages). */
+static void plan_fatal (const char *fn, enum sched_err err, int scan, int size)
 {
-    return order_sensitive (op, dtype, size) && size <= MI355_ORDERS_MAX_SOURCES;
+    switch (err) {
+    case SCHED_OK:
+        return;
+    case SCHED_E_ORDER_AREA:
+        shmemi_fatal ("SHMEM_DEVICE_ORDER_SIZE (%zu bytes per channel) is too small for %d PEs", shmemi.order_chunk,
+                      size);
+    case SCHED_E_P2P_BROKEN:
+        if (scan)
+            shmemi_fatal ("peer GPU memory reads failed the init self-test; the scan collectives need them");
+        shmemi_fatal ("peer GPU memory reads failed the init self-test; only the RCCL pairs "
+                      "(sum/prod/min/max on short/int/long/float/double, complex sum) over all PEs can run");
+    case SCHED_E_STREAM_MEMBERS:
+        shmemi_fatal ("%s: stream-ordered collectives take at most %d PEs per active set (of at most %d)",
+                      fn, MI355_FUSED_MAX_MEMBERS, MI355_SIG_RSDONE);
+    case SCHED_E_STREAM_PEERS:
+        shmemi_fatal ("%s: peer GPU memory failed the init self-test", fn);
+    case SCHED_E_STREAM_OVERLAP:
+        shmemi_fatal ("%s: target and source overlap without being equal", fn);
+    case SCHED_E_STREAM_ORDER:
+        shmemi_fatal ("%s: %d PEs: the stream-ordered schedules deliver each PE's reference order up to %d "
+                      "PEs (set SHMEM_REDUCE_ORDER=pe_start)", fn, size, MI355_ORDERS_MAX_SOURCES);
+    }
 }
 
-/* Two members, float or double sum/prod, each member's own order: the
- * members' results differ only where both operands are NaNs (SSE keeps the
- * first). The multi-launch schedules then skip the version areas: each owner
- * folds its shard in ITS order (own source first) and the other member
- * gathers it NaN-patched from its own source (mi355_nan_patch_copy): one
- * output per shard, one more local read in the gather. (Complex types keep
- * the version areas: the imaginary part of gcc's float complex add takes the
- * incoming operand first, and Annex G's product is not a plain pair.) */
-static int nan_pair (int op, int dtype, const struct aset *s)
-{
-    return shmemi.order == SHMEMX_ORDER_REFERENCE && s->size == 2 && (dtype == MI355_FLOAT || dtype == MI355_DOUBLE) &&
-           (op == MI355_OP_SUM || op == MI355_OP_PROD);
-}
-
-/* Version areas: on every PE, one per signal-region channel, (size - 1)
- * slots of one shard each; slot s of owner i holds member q's version of
- * shard i, s = q < i ? q : q - 1. Each slot starts at the target's offset
- * within 256 bytes, so the gather copies run as aligned vectors.
- * Consecutive slots are VER_STAGGER bytes further apart than a shard needs:
- * the every-member fold writes all its outputs at the same element offset,
- * and outputs a power-of-two shard size apart land in the same HBM channels
- * (tools/probes/cold_probe orders_skew2, 8 x 32 MiB double sum: 0.62 of peak from
- * HBM with 256-byte gaps, 0.68-0.70 with 4 KiB-granular ones). */
-#define VER_STAGGER 4096
-static size_t ver_slot_bytes (size_t n, size_t es, int size)
-{
-    const size_t b = shard_chunk (n, es, size) * es;
-    return (b + 255) / 256 * 256 + 256 + VER_STAGGER;
-}
-
+/* Where member q's version of the owner's shard lies in the owner's version
+ * area on channel chan (sched_plan.h, ver_slot_bytes). */
 static size_t ver_off (int chan, int owner, int q, size_t slot_bytes, size_t dst_off)
 {
     return shmemi.order_off + (size_t) chan * shmemi.order_chunk + (size_t) (q < owner ? q : q - 1) * slot_bytes +
            (dst_off & 255);
-}
-
-/* Elements per round of an ordered P2P reduction: the largest message whose
- * versions fit one channel's version area (longer messages run in rounds). */
-static size_t ordered_round_elems (size_t es, int size)
-{
-    const size_t align = es >= 256 ? 1 : 256 / es;
-    const size_t per_slot = shmemi.order_chunk / (size_t) (size - 1);
-    if (per_slot < 512 + VER_STAGGER + align * es)
-        shmemi_fatal ("SHMEM_DEVICE_ORDER_SIZE (%zu bytes per channel) is too small for %d PEs", shmemi.order_chunk,
-                      size);
-    return (per_slot - 512 - VER_STAGGER) / es / align * align * (size_t) size;
 }
 
 /* ---------------------------------------------------------------------- */
@@ -298,13 +256,6 @@ static void member_args (MI355FusedArgs *a, const struct aset *s, int chan)
     a->no_acquire = shmemi.fused_no_acquire;
 }
 
-/* The device-flag kernels can carry this active set's synchronization. */
-static int device_flags_ok (const struct aset *s)
-{
-    return s->size <= MI355_FUSED_MAX_MEMBERS && shmemi.npes <= MI355_SIG_RSDONE && shmemi.sigmem != NULL &&
-           !shmemi.sig_broken && !shmemi.dev_wait_slow;
-}
-
 static void device_barrier (const MI355FusedArgs *a, hipStream_t st)
 {
     shmemi_server_stop (); /* two spin-waiting grids need not fit beside each other */
@@ -324,8 +275,8 @@ void shmemi_member_args (MI355FusedArgs *a, int PE_start, int stride, int PE_siz
  * (host channel); `last` makes it carry the completion flag and waits. */
 int shmemi_dev_barrier_ok (int PE_start, int stride, int PE_size)
 {
-    struct aset s = {PE_start, stride, PE_size, 0};
-    return device_flags_ok (&s);
+    const struct sched_env e = sched_env_now ();
+    return device_flags_ok (&e, PE_size);
 }
 
 void shmemi_dev_barrier (int PE_start, int stride, int PE_size, int me, int last)
@@ -528,9 +479,6 @@ static void stream_copy (const char *fn, void *const *dsts, const void *const *s
  *   LEGS_PAIR    fold_shard, this owner's order           pair_gather (NaN-patched)
  *   LEGS_INSCAN  scan_fold_shard                          segments from their version areas
  *   LEGS_EXSCAN  scan_fold_shard                          the same; member 0 gathers nothing */
-enum shard_sync { SYNC_HOST, SYNC_DEV, SYNC_STREAM };
-enum shard_legs { LEGS_FOLD, LEGS_ORDERS, LEGS_PAIR, LEGS_INSCAN, LEGS_EXSCAN };
-
 struct shard_call {
     int op, dtype;
     size_t es;
@@ -652,48 +600,35 @@ static void shard_rounds (const struct shard_call *c, size_t dst_off, size_t src
     } while (b < n);
 }
 
-/* The multi-launch P2P schedule of a reduction over [0, n). */
-static void p2p_any (int op, int dtype, size_t es, size_t dst_off, size_t src_off, size_t n, const struct aset *s)
+/* A plan's shard schedule over [0, n), on the library stream or (SYNC_STREAM,
+ * with the entry point's name) the caller's. */
+static void run_shards (const struct sched_plan *p, const struct sched_req *r, const struct aset *s, hipStream_t st,
+                        const char *fn)
 {
-    const int pair = nan_pair (op, dtype, s);
-    const int ordered = ordered_pair (op, dtype, s->size) && !pair;
-    const int dev = device_flags_ok (s);
-    const size_t round = ordered ? ordered_round_elems (es, s->size) : n;
-    SHMEMI_TRACE (SHMEMI_LOG_REDUCTION, "schedule: P2P shards, %s barriers, %s (%zu elements, %d members%s)",
-                  dev ? "device" : "host",
-                  pair      ? "each member's reference order (own-order fold, NaN-patched gather)"
-                  : ordered ? "every member's reference order"
-                            : "PE_start order",
-                  n, s->size, ordered && n > round ? ", several rounds" : "");
-    begin_call (dev ? (n > round ? "p2p-rounds" : "p2p") : (n > round ? "p2p-host-rounds" : "p2p-host"));
-    const struct shard_call c = {op, dtype, es, s, pair ? LEGS_PAIR : ordered ? LEGS_ORDERS : LEGS_FOLD,
-                                 dev ? SYNC_DEV : SYNC_HOST, shmemi.stream, NULL};
-    shard_rounds (&c, dst_off, src_off, n, round);
+    begin_call (sched_name (p->sched));
+    const struct shard_call c = {r->op, r->dtype, r->es, s, p->legs, p->sync, st, fn};
+    shard_rounds (&c, r->dst_off, r->src_off, r->n, p->round);
 }
 
-/* The fused one-launch schedule (fused.hip) applies: small enough, few
- * enough members, 16-byte aligned symmetric offsets, dst == src or disjoint,
- * and (ordered) the versions fit the version area. */
-static int fused_eligible (int op, int dtype, size_t es, size_t dst_off, size_t src_off, size_t n,
-                           const struct aset *s)
+/* The fused kernel's arguments for n elements at the members' symmetric
+ * offsets on channel `chan`. Ordered two-shot calls read and write the
+ * members' version areas of that channel (mi355_reduce.h). */
+static void fused_args (MI355FusedArgs *a, int op, int dtype, size_t es, size_t dst_off, size_t src_off, size_t n,
+                        int ordered, int oneshot, const struct aset *s, int chan)
 {
-    return fused_dtype (dtype) && s->size > 1 && s->size <= MI355_FUSED_MAX_MEMBERS && n * es <= shmemi.fused_max &&
-           shmemi.npes <= MI355_SIG_RSDONE &&
-           shmemi.sigmem != NULL && ((dst_off | src_off) & 15) == 0 && es <= 256 &&
-           (dst_off == src_off || !ranges_overlap (dst_off, src_off, n * es)) &&
-           shmemi.algorithm != SHMEMX_REDUCE_EXACT &&
-           (!ordered_pair (op, dtype, s->size) ||
-            (size_t) (s->size - 1) * shard_chunk (n, es, s->size) * es <= shmemi.order_chunk);
-}
-
-/* The fused kernel's result order: ordered two-shot calls read and write the
- * members' version areas of channel `chan` (mi355_reduce.h). */
-static void fused_order (MI355FusedArgs *a, const struct aset *s, int chan)
-{
-    a->ordered = ordered_pair (a->op, a->dtype, s->size);
-    if (a->ordered && !a->oneshot)
-        for (int i = 0; i < s->size; ++i)
-            a->ver[i] = shmemi_peer_ptr (aset_pe (s, i), shmemi.order_off + (size_t) chan * shmemi.order_chunk);
+    member_args (a, s, chan);
+    a->op = op;
+    a->dtype = dtype;
+    a->n = n;
+    a->shard = shard_chunk (n, es, s->size);
+    a->oneshot = oneshot;
+    a->ordered = ordered;
+    for (int i = 0; i < s->size; ++i) {
+        a->src[i] = shmemi_peer_ptr (a->pe[i], src_off);
+        a->dst[i] = shmemi_peer_ptr (a->pe[i], dst_off);
+        if (ordered && !oneshot)
+            a->ver[i] = shmemi_peer_ptr (a->pe[i], shmemi.order_off + (size_t) chan * shmemi.order_chunk);
+    }
 }
 
 /* The fused kernel's bytes: one-shot = every member's whole source read
@@ -731,11 +666,10 @@ static void note_fused (int size, int ordered, int oneshot, size_t n, size_t es,
  * shmemx_device_synchronize, host heap changes, finalize). Not ordered after
  * the caller's queued GPU work: the caller's writes to the source must be
  * complete (synchronized) before the call -- hence opt-in. */
-static int server_matches (int op, int dtype, const struct aset *s)
+static int server_matches (int op, int dtype, int ordered, const struct aset *s)
 {
     return shmemi.srv.running && shmemi.srv.op == op && shmemi.srv.dtype == dtype && shmemi.srv.start == s->start &&
-           shmemi.srv.stride == s->stride && shmemi.srv.size == s->size &&
-           shmemi.srv.ordered == ordered_pair (op, dtype, s->size);
+           shmemi.srv.stride == s->stride && shmemi.srv.size == s->size && shmemi.srv.ordered == ordered;
 }
 
 /* The server has left (EXITED): later servers start past its last seq. */
@@ -825,21 +759,12 @@ static int server_call (size_t dst_off, size_t src_off, size_t n, size_t shard, 
     }
 }
 
-static void server_start (int op, int dtype, size_t es, size_t n, int oneshot, const struct aset *s)
+static void server_start (int op, int dtype, size_t es, size_t n, int ordered, int oneshot, const struct aset *s)
 {
+    /* the members' heaps and version areas; offsets, sizes and the one-shot flag come by mailbox */
     MI355FusedArgs a;
-    member_args (&a, s, SHMEMI_CHAN_HOST);
-    a.op = op;
-    a.dtype = dtype;
-    for (int i = 0; i < s->size; ++i) {
-        a.src[i] = shmemi_peer_ptr (a.pe[i], 0);
-        a.dst[i] = shmemi_peer_ptr (a.pe[i], 0);
-    }
+    fused_args (&a, op, dtype, es, 0, 0, 0, ordered, 0, s, SHMEMI_CHAN_HOST);
     a.host_flag = shmemi.sig_flag;
-    a.ordered = ordered_pair (op, dtype, s->size);
-    if (a.ordered)
-        for (int i = 0; i < s->size; ++i)
-            a.ver[i] = shmemi_peer_ptr (a.pe[i], shmemi.order_off + (size_t) SHMEMI_CHAN_HOST * shmemi.order_chunk);
     MI355ServerMailbox *mb = shmemi.srv.mb;
     mb->state = MI355_SERVER_RUNNING;
     mb->state_seq = 0;
@@ -869,97 +794,67 @@ static void server_start (int op, int dtype, size_t es, size_t n, int oneshot, c
 
 static void copy_local (size_t dst_off, size_t src_off, size_t nbytes, int timed);
 
-static void fused_launch (int op, int dtype, size_t es, size_t n, const struct aset *s, const void *const *srcs,
-                          void *const *dsts, int same, const void *host_src, void *host_dst);
-
-/* host_src/host_dst: device-accessible page-locked host buffers of this PE
- * staged in-kernel into src_off / out of dst_off (mi355_reduce.h), or NULL.
- * A one-member set (the 1-PE identity copy) comes here only with the
- * persistent server enabled: served, or else one copy kernel. */
-static void fused_range (int op, int dtype, size_t es, size_t dst_off, size_t src_off, size_t n,
-                         const struct aset *s, const void *host_src, void *host_dst)
+/* One launch of the fused kernel over the members' buffers, waited for. */
+static void fused_launch (const struct sched_plan *p, const struct sched_req *r, const struct aset *s,
+                          const void *host_src, void *host_dst)
 {
-    const int servable = shmemi.srv.enabled && host_src == NULL && host_dst == NULL && dst_off < SHMEMI_EXT_TARGET &&
-                         src_off < SHMEMI_EXT_TARGET; /* it addresses the members' heaps */
-    const double t_call = servable ? shmemi_now () : 0.0;
-    if (servable && server_matches (op, dtype, s) && n <= 2 * shmemi.srv.grid_elems) {
+    SHMEMI_TRACE (SHMEMI_LOG_REDUCTION, "schedule: fused one-launch P2P, %s, %s (%zu elements, %d members)%s",
+                  p->oneshot ? "one-shot" : "reduce-scatter + all-gather",
+                  p->ordered ? "every member's reference order" : "PE_start order", r->n, s->size,
+                  host_src != NULL ? ", staging host buffers in-kernel" : "");
+    MI355FusedArgs a;
+    fused_args (&a, r->op, r->dtype, r->es, r->dst_off, r->src_off, r->n, p->ordered, p->oneshot, s, SHMEMI_CHAN_HOST);
+    a.host_flag = shmemi.sig_flag;
+    a.epoch = shmemi_next_epoch ();
+    a.host_src = host_src;
+    a.host_dst = host_dst;
+    shmemi_timed_begin (); /* the call's one (dominant) kernel */
+    const int rc = mi355_fused_allreduce (&a, shmemi.stream);
+    shmemi_timed_end ();
+    if (rc != 0)
+        shmemi_fatal ("fused reduction launch failed (op %d, dtype %d, %d PEs, %zu elements): %d", r->op, r->dtype,
+                      s->size, r->n, rc);
+    begin_call (sched_name (p->sched));
+    note_fused (s->size, a.ordered, a.oneshot, r->n, r->es, mi355_last_kernel ());
+    if (shmemi_wait_flag (a.epoch) != a.epoch)
+        shmemi_fatal ("fused reduction timed out waiting for the other PEs of the active set");
+}
+
+static void identity_copy (const struct sched_req *r)
+{
+    SHMEMI_TRACE (SHMEMI_LOG_REDUCTION, "schedule: 1-PE identity, one copy of %zu bytes", r->n * r->es);
+    begin_call (sched_name (SCHED_IDENTITY));
+    copy_local (r->dst_off, r->src_off, r->n * r->es, 1);
+}
+
+/* A fused plan, or the one-member copy of a servable one: by the persistent
+ * server where the plan allows it and the server matches, else launched.
+ * host_src/host_dst: device-accessible page-locked host buffers of this PE
+ * staged in-kernel into src_off / out of dst_off (mi355_reduce.h), or NULL. */
+static void fused_range (const struct sched_plan *p, const struct sched_req *r, const struct aset *s,
+                         const void *host_src, void *host_dst)
+{
+    const size_t n = r->n;
+    const double t_call = p->servable ? shmemi_now () : 0.0;
+    if (p->servable && server_matches (r->op, r->dtype, p->ordered, s) && n <= 2 * shmemi.srv.grid_elems) {
         SHMEMI_TRACE (SHMEMI_LOG_REDUCTION, "schedule: persistent fused server (%zu elements, %d members)", n, s->size);
-        const int oneshot = n * es <= shmemi.oneshot_max && dst_off != src_off;
-        if (server_call (dst_off, src_off, n, shard_chunk (n, es, s->size), oneshot)) {
+        if (server_call (r->dst_off, r->src_off, n, shard_chunk (n, r->es, s->size), p->oneshot)) {
             shmemi.srv.last_end = shmemi_now ();
-            begin_call ("persistent");
-            note_fused (s->size, shmemi.srv.ordered, oneshot, n, es, shmemi.srv.kernel);
+            begin_call (sched_name (SCHED_PERSISTENT));
+            note_fused (s->size, shmemi.srv.ordered, p->oneshot, n, r->es, shmemi.srv.kernel);
             return;
         }
     }
     shmemi_server_stop (); /* a different call: the launched grid must fit */
-    if (s->size == 1) {
-        SHMEMI_TRACE (SHMEMI_LOG_REDUCTION, "schedule: 1-PE identity, one copy of %zu bytes", n * es);
-        begin_call ("identity");
-        copy_local (dst_off, src_off, n * es, 1);
-    } else {
-        const void *srcs[MI355_FUSED_MAX_MEMBERS];
-        void *dsts[MI355_FUSED_MAX_MEMBERS];
-        for (int i = 0; i < s->size; ++i) {
-            srcs[i] = shmemi_peer_ptr (aset_pe (s, i), src_off);
-            dsts[i] = shmemi_peer_ptr (aset_pe (s, i), dst_off);
-        }
-        fused_launch (op, dtype, es, n, s, srcs, dsts, dst_off == src_off, host_src, host_dst);
-    }
-    if (servable) {
+    if (s->size == 1)
+        identity_copy (r);
+    else
+        fused_launch (p, r, s, host_src, host_dst);
+    if (p->servable) {
         /* the second call of a burst leaves the kernel resident for the next */
         if (shmemi.srv.last_end >= 0.0 && t_call - shmemi.srv.last_end < shmemi.srv.idle_s)
-            server_start (op, dtype, es, n, n * es <= shmemi.oneshot_max && dst_off != src_off, s);
+            server_start (r->op, r->dtype, r->es, n, p->ordered, p->oneshot, s);
         shmemi.srv.last_end = shmemi_now ();
-    }
-}
-
-/* One launch of the fused kernel over the members' buffers srcs[i] / dsts[i]
- * (this PE's = member s->me's), waited for. `same`: target = source (no
- * one-shot: it would overwrite a source others still read). */
-static void fused_launch (int op, int dtype, size_t es, size_t n, const struct aset *s, const void *const *srcs,
-                          void *const *dsts, int same, const void *host_src, void *host_dst)
-{
-    {
-        SHMEMI_TRACE (SHMEMI_LOG_REDUCTION, "schedule: fused one-launch P2P, %s, %s (%zu elements, %d members)%s",
-                      n * es <= shmemi.oneshot_max && !same ? "one-shot" : "reduce-scatter + all-gather",
-                      ordered_pair (op, dtype, s->size) ? "every member's reference order" : "PE_start order", n,
-                      s->size, host_src != NULL ? ", staging host buffers in-kernel" : "");
-        MI355FusedArgs a;
-        memset (&a, 0, sizeof a);
-        a.op = op;
-        a.dtype = dtype;
-        a.nmembers = s->size;
-        a.me = s->me;
-        a.n = n;
-        a.shard = shard_chunk (n, es, s->size);
-        for (int i = 0; i < s->size; ++i) {
-            const int pe = aset_pe (s, i);
-            a.pe[i] = pe;
-            a.src[i] = srcs[i];
-            a.dst[i] = dsts[i];
-            a.sig[i] = shmemi.peer_sig[pe] + SHMEMI_CHAN_HOST * MI355_SIG_CHANNEL_WORDS;
-        }
-        a.host_flag = shmemi.sig_flag;
-        a.epoch = shmemi_next_epoch ();
-        a.err_flag = shmemi.stream_err;
-        a.timeout_ticks = (unsigned long long) (shmemi.barrier_timeout * 1e8);
-        a.host_src = host_src;
-        a.host_dst = host_dst;
-        a.share = shmemi.local_pes;
-        a.no_acquire = shmemi.fused_no_acquire;
-        a.oneshot = n * es <= shmemi.oneshot_max && !same;
-        fused_order (&a, s, SHMEMI_CHAN_HOST);
-        shmemi_timed_begin (); /* the call's one (dominant) kernel */
-        const int rc = mi355_fused_allreduce (&a, shmemi.stream);
-        shmemi_timed_end ();
-        if (rc != 0)
-            shmemi_fatal ("fused reduction launch failed (op %d, dtype %d, %d PEs, %zu elements): %d", op, dtype,
-                          s->size, n, rc);
-        begin_call (a.oneshot ? "fused-oneshot" : "fused-twoshot");
-        note_fused (s->size, a.ordered, a.oneshot, n, es, mi355_last_kernel ());
-        if (shmemi_wait_flag (a.epoch) != a.epoch)
-            shmemi_fatal ("fused reduction timed out waiting for the other PEs of the active set");
     }
 }
 
@@ -993,87 +888,23 @@ static void copy_local (size_t dst_off, size_t src_off, size_t nbytes, int timed
         note_call (0, 1, 1, 0, (unsigned long long) nbytes, 0, 0, mi355_last_kernel ());
 }
 
-/* Reduce n elements at symmetric offsets. Handles aliasing like the
- * reference's temporary target (reduce-op.c:174-215), but chunked through
- * scratch in memmove order so any overlap is safe. */
+/* One blocking request at symmetric offsets: planned, traced, executed. */
+static void run_blocking (const struct sched_req *r, const struct aset *s);
+
+static struct sched_req blocking_req (enum sched_coll coll, int op, int dtype, size_t es, size_t dst_off,
+                                      size_t src_off, size_t n, const struct aset *s)
+{
+    const struct sched_req r = {coll, ENTRY_BLOCKING, op, dtype, es, dst_off, src_off, n, s->size, s->me,
+                                dst_off < SHMEMI_EXT_TARGET && src_off < SHMEMI_EXT_TARGET, 0};
+    return r;
+}
+
+/* Reduce n elements at symmetric offsets. */
 static void reduce_symmetric (int op, int dtype, size_t es, size_t dst_off, size_t src_off, size_t n,
                               const struct aset *s)
 {
-    const size_t nbytes = n * es;
-    /* EXACT by request, or for an order-sensitive set too large for the
-     * shard schedules' every-order fold (ordered_pair) */
-    const int exact = shmemi.algorithm == SHMEMX_REDUCE_EXACT ||
-                      (order_sensitive (op, dtype, s->size) && !ordered_pair (op, dtype, s->size));
-    const int same = dst_off == src_off;
-    if (s->size > 1 && shmemi.p2p_broken)
-        shmemi_fatal ("peer GPU memory reads failed the init self-test; only the RCCL pairs "
-                      "(sum/prod/min/max on short/int/long/float/double, complex sum) over all PEs can run");
-    const int overlap = ranges_overlap (dst_off, src_off, nbytes);
-
-    if (s->size == 1) {
-        /* a one-PE fold is the identity: target = source (reduce-op.c:226-229) */
-        if (same) {
-            SHMEMI_TRACE (SHMEMI_LOG_REDUCTION, "schedule: 1-PE identity in place, nothing to move");
-            begin_call ("identity");
-            return;
-        }
-        if (!overlap) {
-            if (shmemi.srv.enabled && fused_dtype (dtype) && nbytes <= shmemi.fused_max &&
-                ((dst_off | src_off) & 15) == 0) {
-                fused_range (op, dtype, es, dst_off, src_off, n, s, NULL, NULL); /* persistent server */
-                return;
-            }
-            SHMEMI_TRACE (SHMEMI_LOG_REDUCTION, "schedule: 1-PE identity, one copy of %zu bytes", nbytes);
-            begin_call ("identity");
-            copy_local (dst_off, src_off, nbytes, 1);
-            return;
-        }
-    } else if (!exact && (same || !overlap)) {
-        if (fused_eligible (op, dtype, es, dst_off, src_off, n, s))
-            fused_range (op, dtype, es, dst_off, src_off, n, s, NULL, NULL);
-        else
-            p2p_any (op, dtype, es, dst_off, src_off, n, s);
-        return;
-    } else if (exact && !overlap) {
-        SHMEMI_TRACE (SHMEMI_LOG_REDUCTION, "schedule: EXACT reference order, host barriers");
-        begin_call ("exact");
-        host_order ();
-        shmemi_barrier_set (s->start, s->stride, s->size);
-        exact_into (op, dtype, dst_off, src_off, n, s);
-        shmemi_barrier_set (s->start, s->stride, s->size);
-        return;
-    }
-
-    /* overlapping target/source: through scratch buffer C, chunk by chunk,
-     * walking down when target lies above source (memmove order) */
-    const size_t tmp_off = shmemi.scratch_off + 2 * shmemi.scratch_chunk;
-    const size_t per = shmemi.scratch_chunk / es;
-    const size_t nchunks = (n + per - 1) / per;
-    const int down = dst_off > src_off;
-    SHMEMI_TRACE (SHMEMI_LOG_REDUCTION, "schedule: overlapping target, %zu chunk(s) through scratch, %s", nchunks,
-                  down ? "top down" : "bottom up");
-    if (s->size == 1 || exact)
-        begin_call (exact ? "exact" : "identity");
-    for (size_t c = 0; c < nchunks; ++c) {
-        const size_t idx = down ? nchunks - 1 - c : c;
-        const size_t b = idx * per;
-        const size_t cn = n - b < per ? n - b : per;
-        if (s->size == 1) {
-            copy_local (tmp_off, src_off + b * es, cn * es, 0);
-        } else if (!exact) {
-            p2p_any (op, dtype, es, tmp_off, src_off + b * es, cn, s);
-        } else {
-            host_order ();
-            shmemi_barrier_set (s->start, s->stride, s->size);
-            exact_into (op, dtype, tmp_off, src_off + b * es, cn, s);
-            shmemi_barrier_set (s->start, s->stride, s->size);
-        }
-        copy_local (dst_off + b * es, tmp_off, cn * es, 0);
-        /* nobody reads our target chunk; the next chunk's first barrier orders
-         * our write before any peer reads the source bytes it may cover */
-    }
-    if (s->size > 1)
-        shmemi_barrier_set (s->start, s->stride, s->size);
+    const struct sched_req r = blocking_req (COLL_REDUCE, op, dtype, es, dst_off, src_off, n, s);
+    run_blocking (&r, s);
 }
 
 /* ---------------------------------------------------------------------- */
@@ -1220,10 +1051,14 @@ static int local_direct (int op, int dtype, void *target, const void *source, si
     const size_t half = shmemi.scratch_chunk / 2 / SHMEMI_ALIGN * SHMEMI_ALIGN;
     if (nbytes > SHMEMI_SMALL_LOCAL_MAX || nbytes > half)
         return 0;
-    const size_t a_off = shmemi.scratch_off, b_off = shmemi.scratch_off + shmemi.scratch_chunk;
-    if (!fused_eligible (op, dtype, es, b_off, a_off, n, s))
+    struct sched_req r = blocking_req (COLL_REDUCE, op, dtype, es, shmemi.scratch_off + shmemi.scratch_chunk,
+                                       shmemi.scratch_off, n, s);
+    r.in_heap = 0; /* this PE's two sides are its host buffers */
+    const struct sched_env e = sched_env_now ();
+    const struct sched_plan p = plan_schedule (&e, &r);
+    if (p.sched != SCHED_FUSED_ONESHOT && p.sched != SCHED_FUSED_TWOSHOT)
         return 0;
-    fused_range (op, dtype, es, b_off, a_off, n, s, hs, ht);
+    fused_range (&p, &r, s, hs, ht);
     return 1;
 }
 
@@ -1496,11 +1331,8 @@ static void stream_begin (const char *fn)
 static void stream_aset (const char *fn, struct aset *s, int PE_start, int logPE_stride, int PE_size)
 {
     aset_init (fn, s, PE_start, logPE_stride, PE_size);
-    if (PE_size > MI355_FUSED_MAX_MEMBERS || shmemi.npes > MI355_SIG_RSDONE)
-        shmemi_fatal ("%s: stream-ordered collectives take at most %d PEs per active set (of at most %d)",
-                      fn, MI355_FUSED_MAX_MEMBERS, MI355_SIG_RSDONE);
-    if (PE_size > 1 && (shmemi.sigmem == NULL || shmemi.p2p_broken || shmemi.sig_broken))
-        shmemi_fatal ("%s: peer GPU memory failed the init self-test", fn);
+    const struct sched_env e = sched_env_now ();
+    plan_fatal (fn, stream_set_error (&e, PE_size), 0, PE_size);
 }
 
 static void reduce_on_stream (int op, int dtype, const char *fn, void *target, const void *source, int nreduce,
@@ -1518,56 +1350,41 @@ static void reduce_on_stream (int op, int dtype, const char *fn, void *target, c
     if (n > 0 && (target == NULL || source == NULL || !shmemi_in_device_heap (target, nbytes) ||
                   !shmemi_in_device_heap (source, nbytes)))
         shmemi_fatal ("%s: target and source must lie in the device symmetric heap (shmemx_malloc_device)", fn);
-    if (n > 0 && target != source && ranges_overlap ((size_t) target, (size_t) source, nbytes))
-        shmemi_fatal ("%s: target and source overlap without being equal", fn);
     if (shmemi.debug)
         debug_check (fn, op, dtype, target, source, nreduce, PE_start, logPE_stride, PE_size);
 
-    if (n == 0) {
-        begin_call ("barrier-only");
+    const struct sched_req r = {COLL_REDUCE, ENTRY_STREAM, op, dtype, es, n > 0 ? shmemi_heap_offset (target) : 0,
+                                n > 0 ? shmemi_heap_offset (source) : 0, n, s.size, s.me, 1, 0};
+    const struct sched_env e = sched_env_now ();
+    const struct sched_plan p = plan_schedule (&e, &r);
+    plan_fatal (fn, p.err, 0, s.size);
+    switch (p.sched) {
+    case SCHED_BARRIER_ONLY:
+        begin_call (sched_name (p.sched));
         stream_barrier (fn, &s, st);
-    } else if (s.size == 1) {
-        begin_call ("stream-identity");
-        if (target != source) {
+        break;
+    case SCHED_STREAM_IDENTITY:
+        begin_call (sched_name (p.sched));
+        if (!p.noop) {
             void *d = target;
             const void *sv = source;
             stream_copy (fn, &d, &sv, &nbytes, 1, st);
             note_call (0, 1, 1, 0, (unsigned long long) nbytes, 0, 0, mi355_last_kernel ());
         }
-    } else {
-        const size_t dst_off = shmemi_heap_offset (target), src_off = shmemi_heap_offset (source);
+        break;
+    case SCHED_STREAM_FUSED_ONESHOT:
+    case SCHED_STREAM_FUSED_TWOSHOT: {
         MI355FusedArgs a;
-        member_args (&a, &s, SHMEMI_CHAN_STREAM);
-        const int ordered = ordered_pair (op, dtype, s.size);
-        if (order_sensitive (op, dtype, s.size) && !ordered)
-            shmemi_fatal ("%s: %d PEs: the stream-ordered schedules deliver each PE's reference order up to %d "
-                          "PEs (set SHMEM_REDUCE_ORDER=pe_start)", fn, s.size, MI355_ORDERS_MAX_SOURCES);
-        if (fused_dtype (dtype) && n * es <= shmemi.fused_max && ((dst_off | src_off) & 15) == 0 && es <= 256 &&
-            (!ordered || (size_t) (s.size - 1) * shard_chunk (n, es, s.size) * es <= shmemi.order_chunk)) {
-            a.op = op;
-            a.dtype = dtype;
-            a.n = n;
-            a.shard = shard_chunk (n, es, s.size);
-            for (int i = 0; i < s.size; ++i) {
-                a.src[i] = shmemi_peer_ptr (a.pe[i], src_off);
-                a.dst[i] = shmemi_peer_ptr (a.pe[i], dst_off);
-            }
-            a.oneshot = n * es <= shmemi.oneshot_max && dst_off != src_off;
-            fused_order (&a, &s, SHMEMI_CHAN_STREAM);
-            const int rc = mi355_fused_allreduce (&a, st);
-            if (rc != 0)
-                shmemi_fatal ("%s: fused reduction launch failed: %d", fn, rc);
-            begin_call (a.oneshot ? "stream-fused-oneshot" : "stream-fused-twoshot");
-            note_fused (s.size, a.ordered, a.oneshot, n, es, mi355_last_kernel ());
-        } else {
-            const int pair = nan_pair (op, dtype, &s);
-            const int ord = ordered && !pair;
-            const size_t round = ord ? ordered_round_elems (es, s.size) : n;
-            begin_call (n > round ? "stream-p2p-rounds" : "stream-p2p");
-            const struct shard_call c = {op, dtype, es, &s, pair ? LEGS_PAIR : ord ? LEGS_ORDERS : LEGS_FOLD,
-                                         SYNC_STREAM, st, fn};
-            shard_rounds (&c, dst_off, src_off, n, round);
-        }
+        fused_args (&a, op, dtype, es, r.dst_off, r.src_off, n, p.ordered, p.oneshot, &s, SHMEMI_CHAN_STREAM);
+        const int rc = mi355_fused_allreduce (&a, st);
+        if (rc != 0)
+            shmemi_fatal ("%s: fused reduction launch failed: %d", fn, rc);
+        begin_call (sched_name (p.sched));
+        note_fused (s.size, a.ordered, a.oneshot, n, es, mi355_last_kernel ());
+        break;
+    }
+    default: /* SCHED_STREAM_P2P, SCHED_STREAM_P2P_ROUNDS */
+        run_shards (&p, &r, &s, st, fn);
     }
 }
 
@@ -1690,24 +1507,8 @@ SHMEMX_REDUCE_TYPE (bfloat16, MI355_BFLOAT16)
  * (mi355_reduce.h). In place that is inscan's shard fold; exscan in place
  * (the owner's prefix me - 1 would land on source me), the direct schedule
  * in place (the target would be the fold's last source) and partially
- * overlapping buffers go through scratch buffer C, as reduce_symmetric's
+ * overlapping buffers go through scratch buffer C, as a reduction's
  * overlapping calls do. */
-#include "prefix_plan.h"
-
-static int scan_direct_forced (void)
-{
-    static int forced = -1;
-    if (forced < 0) {
-        const char *e = getenv ("SHMEM_SCAN_DIRECT");
-        forced = e != NULL && atoi (e) != 0;
-    }
-    return forced;
-}
-
-static int scan_is_direct (const struct aset *s)
-{
-    return s->size > MI355_ORDERS_MAX_SOURCES || scan_direct_forced ();
-}
 
 /* The owner's leg: every prefix of this PE's shard. 0: queued, or nothing
  * to do (an empty shard). */
@@ -1762,78 +1563,120 @@ static void scan_direct (int op, int dtype, size_t es, size_t dst_off, size_t sr
     shmemi_barrier_set (s->start, s->stride, s->size); /* peers are done reading us */
 }
 
-/* One scan of [0, n) at symmetric offsets, dst and src disjoint (or, shard
- * schedule of an inscan, identical); ends with a barrier of the set. */
-static void scan_any (int op, int dtype, size_t es, size_t dst_off, size_t src_off, size_t n, const struct aset *s,
-                      int excl)
+/* ---------------------------------------------------------------------- */
+/* executing a blocking plan                                               */
+/* ---------------------------------------------------------------------- */
+/* An overlap no schedule takes (sched_plan.h, via_scratch): through scratch
+ * buffer C chunk by chunk, each a request of its own into C and one copy
+ * from there, walking down when the target lies above the source (memmove
+ * order) -- like the reference's temporary target (reduce-op.c:174-215), but
+ * safe for any overlap. */
+static void through_scratch (const struct sched_plan *p, const struct sched_req *r, const struct aset *s)
 {
-    if (scan_is_direct (s)) {
-        SHMEMI_TRACE (SHMEMI_LOG_REDUCTION, "schedule: scan, direct: each member folds its prefix of the whole "
-                                            "arrays, host barriers (%zu elements, %d members)", n, s->size);
-        begin_call ("scan-direct");
-        scan_direct (op, dtype, es, dst_off, src_off, n, s, excl);
+    const size_t tmp_off = shmemi.scratch_off + 2 * shmemi.scratch_chunk, per = p->chunk_elems;
+    const size_t nchunks = (r->n + per - 1) / per;
+    SHMEMI_TRACE (SHMEMI_LOG_REDUCTION, "schedule: %s, %zu chunk(s) through scratch, %s",
+                  r->coll == COLL_REDUCE ? "overlapping target" : "scan with overlapping target", nchunks,
+                  p->down ? "top down" : "bottom up");
+    for (size_t c = 0; c < nchunks; ++c) {
+        const size_t b = (p->down ? nchunks - 1 - c : c) * per;
+        struct sched_req cr = *r;
+        cr.chunk = 1;
+        cr.dst_off = tmp_off;
+        cr.src_off = r->src_off + b * r->es;
+        cr.n = r->n - b < per ? r->n - b : per;
+        run_blocking (&cr, s);
+        if (p->receives)
+            copy_local (r->dst_off + b * r->es, tmp_off, cr.n * r->es, 0);
+        /* nobody reads our target chunk; the next chunk's first barrier orders
+         * our write before any peer reads the source bytes it may cover */
+    }
+    if (s->size > 1)
+        shmemi_barrier_set (s->start, s->stride, s->size);
+}
+
+static void run_blocking (const struct sched_req *r, const struct aset *s)
+{
+    const struct sched_env e = sched_env_now ();
+    const struct sched_plan p = plan_schedule (&e, r);
+    const size_t n = r->n, nbytes = n * r->es;
+    const int scan = r->coll != COLL_REDUCE, excl = r->coll == COLL_EXSCAN;
+    const int dev = p.sync == SYNC_DEV;
+    plan_fatal (NULL, p.err, scan, s->size);
+    if (scan && !r->chunk && s->size > 1 &&
+        (shmemi.algorithm == SHMEMX_REDUCE_EXACT || shmemi.algorithm == SHMEMX_REDUCE_RCCL))
+        SHMEMI_TRACE (SHMEMI_LOG_REDUCTION, "scan: the %s request does not apply (a scan has one order and RCCL has "
+                                            "no scan); running the scan schedule",
+                      shmemi.algorithm == SHMEMX_REDUCE_EXACT ? "EXACT" : "RCCL");
+    if (p.sched == SCHED_SCAN_LOCAL && !r->chunk)
+        SHMEMI_TRACE (SHMEMI_LOG_REDUCTION, "schedule: scan of one member: %s",
+                      excl ? "exscan, nothing to do" : r->dst_off == r->src_off ? "inscan in place, nothing to move"
+                                                                                : "inscan, one copy");
+    if (p.via_scratch) {
+        /* one name for the whole walk where the chunks announce none */
+        if (p.sched == SCHED_IDENTITY || p.sched == SCHED_EXACT || p.sched == SCHED_SCAN_LOCAL)
+            begin_call (sched_name (p.sched));
+        through_scratch (&p, r, s);
         return;
     }
-    const int dev = device_flags_ok (s);
-    const size_t round = ordered_round_elems (es, s->size);
-    SHMEMI_TRACE (SHMEMI_LOG_REDUCTION, "schedule: scan, P2P shards, %s barriers, every prefix from one pass "
-                                        "(%zu elements, %d members%s)", dev ? "device" : "host", n, s->size,
-                  n > round ? ", several rounds" : "");
-    begin_call (dev ? (n > round ? "scan-p2p-rounds" : "scan-p2p") : (n > round ? "scan-p2p-host-rounds" : "scan-p2p-host"));
-    const struct shard_call c = {op, dtype, es, s, excl ? LEGS_EXSCAN : LEGS_INSCAN, dev ? SYNC_DEV : SYNC_HOST,
-                                 shmemi.stream, NULL};
-    shard_rounds (&c, dst_off, src_off, n, round);
+    switch (p.sched) {
+    case SCHED_IDENTITY:
+    case SCHED_SCAN_LOCAL:
+        if (r->chunk) {
+            copy_local (r->dst_off, r->src_off, nbytes, 0);
+        } else if (p.servable) {
+            fused_range (&p, r, s, NULL, NULL);
+        } else if (scan || p.noop) {
+            if (!scan)
+                SHMEMI_TRACE (SHMEMI_LOG_REDUCTION, "schedule: 1-PE identity in place, nothing to move");
+            begin_call (sched_name (p.sched));
+            if (!p.noop)
+                copy_local (r->dst_off, r->src_off, nbytes, 1);
+        } else {
+            identity_copy (r);
+        }
+        break;
+    case SCHED_FUSED_ONESHOT:
+    case SCHED_FUSED_TWOSHOT:
+        fused_range (&p, r, s, NULL, NULL);
+        break;
+    case SCHED_EXACT:
+        if (!r->chunk) {
+            SHMEMI_TRACE (SHMEMI_LOG_REDUCTION, "schedule: EXACT reference order, host barriers");
+            begin_call (sched_name (p.sched));
+        }
+        host_order ();
+        shmemi_barrier_set (s->start, s->stride, s->size);
+        exact_into (r->op, r->dtype, r->dst_off, r->src_off, n, s);
+        shmemi_barrier_set (s->start, s->stride, s->size);
+        break;
+    case SCHED_SCAN_DIRECT:
+        SHMEMI_TRACE (SHMEMI_LOG_REDUCTION, "schedule: scan, direct: each member folds its prefix of the whole "
+                                            "arrays, host barriers (%zu elements, %d members)", n, s->size);
+        begin_call (sched_name (p.sched));
+        scan_direct (r->op, r->dtype, r->es, r->dst_off, r->src_off, n, s, excl);
+        break;
+    default: /* the shard schedules */
+        if (scan)
+            SHMEMI_TRACE (SHMEMI_LOG_REDUCTION, "schedule: scan, P2P shards, %s barriers, every prefix from one pass "
+                                                "(%zu elements, %d members%s)", dev ? "device" : "host", n, s->size,
+                          n > p.round ? ", several rounds" : "");
+        else
+            SHMEMI_TRACE (SHMEMI_LOG_REDUCTION, "schedule: P2P shards, %s barriers, %s (%zu elements, %d members%s)",
+                          dev ? "device" : "host",
+                          p.legs == LEGS_PAIR ? "each member's reference order (own-order fold, NaN-patched gather)"
+                          : p.ordered         ? "every member's reference order"
+                                              : "PE_start order",
+                          n, s->size, n > p.round ? ", several rounds" : "");
+        run_shards (&p, r, s, shmemi.stream, NULL);
+    }
 }
 
 static void scan_symmetric (int op, int dtype, size_t es, size_t dst_off, size_t src_off, size_t n,
                             const struct aset *s, int excl)
 {
-    const size_t nbytes = n * es;
-    const int same = dst_off == src_off;
-    const int overlap = ranges_overlap (dst_off, src_off, nbytes);
-    const int receives = !(excl && s->me == 0); /* this member's target is written */
-    if (s->size > 1 && shmemi.p2p_broken)
-        shmemi_fatal ("peer GPU memory reads failed the init self-test; the scan collectives need them");
-    if (s->size > 1 && (shmemi.algorithm == SHMEMX_REDUCE_EXACT || shmemi.algorithm == SHMEMX_REDUCE_RCCL))
-        SHMEMI_TRACE (SHMEMI_LOG_REDUCTION, "scan: the %s request does not apply (a scan has one order and RCCL has "
-                                            "no scan); running the scan schedule",
-                      shmemi.algorithm == SHMEMX_REDUCE_EXACT ? "EXACT" : "RCCL");
-    if (s->size == 1) {
-        SHMEMI_TRACE (SHMEMI_LOG_REDUCTION, "schedule: scan of one member: %s",
-                      excl ? "exscan, nothing to do" : same ? "inscan in place, nothing to move" : "inscan, one copy");
-        begin_call ("scan-local");
-        if (excl || same)
-            return;
-        if (!overlap) {
-            copy_local (dst_off, src_off, nbytes, 1);
-            return;
-        }
-    } else if (!overlap || (same && !excl && !scan_is_direct (s))) {
-        scan_any (op, dtype, es, dst_off, src_off, n, s, excl);
-        return;
-    }
-
-    /* through scratch buffer C, chunk by chunk, walking down when target
-     * lies above source (memmove order), as reduce_symmetric */
-    const size_t tmp_off = shmemi.scratch_off + 2 * shmemi.scratch_chunk;
-    const size_t per = shmemi.scratch_chunk / es;
-    const size_t nchunks = (n + per - 1) / per;
-    const int down = dst_off > src_off;
-    SHMEMI_TRACE (SHMEMI_LOG_REDUCTION, "schedule: scan with overlapping target, %zu chunk(s) through scratch, %s",
-                  nchunks, down ? "top down" : "bottom up");
-    for (size_t c = 0; c < nchunks; ++c) {
-        const size_t idx = down ? nchunks - 1 - c : c;
-        const size_t b = idx * per;
-        const size_t cn = n - b < per ? n - b : per;
-        if (s->size == 1)
-            copy_local (tmp_off, src_off + b * es, cn * es, 0);
-        else
-            scan_any (op, dtype, es, tmp_off, src_off + b * es, cn, s, excl);
-        if (receives)
-            copy_local (dst_off + b * es, tmp_off, cn * es, 0);
-    }
-    if (s->size > 1)
-        shmemi_barrier_set (s->start, s->stride, s->size);
+    const struct sched_req r = blocking_req (excl ? COLL_EXSCAN : COLL_INSCAN, op, dtype, es, dst_off, src_off, n, s);
+    run_blocking (&r, s);
 }
 
 /* Host-heap (shmem_malloc) and other host arrays: each chunk goes into
