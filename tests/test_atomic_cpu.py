@@ -13,12 +13,12 @@ import os
 import re
 import subprocess
 import sys
-import uuid
 
 import pytest
 
 import shmem_reduce
 import test_bootstrap
+from _pes import launch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -156,30 +156,12 @@ def run_workers(npes, heap, tests, tmp_path, gpu=False, timeout=120):
     d.mkdir()
     spec = d / "spec.json"
     spec.write_text(json.dumps({"heap": heap, "tests": tests, "dir": str(d)}))
-    env = dict(os.environ, SHMEM_NPES=str(npes), SHMEM_JOB_ID=uuid.uuid4().hex[:12], SHMEM_BARRIER_TIMEOUT="60",
-               SHMEM_WAIT_TIMEOUT="20")
+    env = dict(SHMEM_BARRIER_TIMEOUT="60", SHMEM_WAIT_TIMEOUT="20")
     if gpu:
-        from test_gpu_multipe import oshrun_queues
-        env.update({"SHMEM_DEVICE": "0", "SHMEM_DEVICE_HEAP_SIZE": "160M", "SHMEM_DEVICE_SCRATCH_SIZE": "3M",
+        env.update({"SHMEM_DEVICE_HEAP_SIZE": "160M", "SHMEM_DEVICE_SCRATCH_SIZE": "3M",
                     "SHMEM_SYMMETRIC_HEAP_SIZE": "16M", "SHMEM_PEER_ACQUIRE": "1"})
-        env.update(oshrun_queues(npes, env))
-    else:
-        env["SHMEM_BOOTSTRAP_ONLY"] = "1"
-    procs = [subprocess.Popen([sys.executable, os.path.join(HERE, "atomic_worker.py"), str(spec)],
-                              env=dict(env, SHMEM_PE=str(pe)), stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
-                              text=True) for pe in range(npes)]
-    outs = []
-    for p in procs:
-        try:
-            out, _ = p.communicate(timeout=timeout)
-        except subprocess.TimeoutExpired:
-            for q in procs:
-                q.kill()
-            raise
-        outs.append((p.returncode, out))
-    for pe, (rc, out) in enumerate(outs):
-        assert rc == 0, f"PE {pe} exited {rc}:\n{out[-3000:]}"
-        rec = json.loads([ln for ln in out.splitlines() if ln.startswith("{")][-1])
+    for rec in launch(npes, [sys.executable, os.path.join(HERE, "atomic_worker.py"), str(spec)], gpu=gpu,
+                      timeout=timeout, env=env).records():
         assert rec["checked"] == tests and not rec["failures"], rec
 
 
@@ -205,13 +187,10 @@ def build_c(tmp_path, source, name):
 
 
 def run_c_host(exe, npes):
-    env = dict(os.environ, SHMEM_BOOTSTRAP_ONLY="1", SHMEM_NPES=str(npes), SHMEM_JOB_ID=uuid.uuid4().hex[:12],
-               SHMEM_BARRIER_TIMEOUT="60", SHMEM_WAIT_TIMEOUT="20")
-    procs = [subprocess.Popen([exe, "host"], env=dict(env, SHMEM_PE=str(pe)), stdout=subprocess.PIPE,
-                              stderr=subprocess.STDOUT, text=True) for pe in range(npes)]
-    outs = [p.communicate(timeout=60)[0] for p in procs]
-    for p, out in zip(procs, outs):
-        assert p.returncode == 0 and ": PASS" in out, out
+    job = launch(npes, [exe, "host"], gpu=False, timeout=60,
+                 env=dict(SHMEM_BARRIER_TIMEOUT="60", SHMEM_WAIT_TIMEOUT="20"))
+    for rc, out in zip(job.rc, job.out):
+        assert rc == 0 and ": PASS" in out, out
 
 
 @pytest.mark.parametrize("npes", [1, 3])

@@ -5,35 +5,33 @@ barriers under random delays and check ordering through a shared file;
 a reduction call without a GPU must abort loudly (there is no CPU path).
 """
 import os
-import subprocess
 import sys
 import textwrap
 import uuid
 
 import pytest
 
+from _pes import launch
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "osss-gasnet_amd")
 
 
+PRELUDE = textwrap.dedent(f"""
+    import os, sys, random, time, ctypes
+    sys.path.insert(0, {PKG!r})
+    import shmem_reduce
+    shm = shmem_reduce.Shmem(); shm.init()
+    me, npes = shm.my_pe(), shm.n_pes()
+""")
+
+
 def spawn(npes, body, tmp_path, timeout=120, extra=None):
-    code = textwrap.dedent(f"""
-        import os, sys, random, time, ctypes
-        sys.path.insert(0, {PKG!r})
-        import shmem_reduce
-        shm = shmem_reduce.Shmem(); shm.init()
-        me, npes = shm.my_pe(), shm.n_pes()
-    """) + textwrap.dedent(body)
-    env = dict(os.environ, SHMEM_BOOTSTRAP_ONLY="1", SHMEM_NPES=str(npes), SHMEM_JOB_ID=uuid.uuid4().hex[:12],
-               SHMEM_BARRIER_TIMEOUT="60", TMPDIR=str(tmp_path))
+    """PRELUDE + body on npes PEs without a GPU: [(exit status, output)]"""
+    env = dict(SHMEM_BARRIER_TIMEOUT="60", TMPDIR=str(tmp_path))
     env.update(extra or {})
-    procs = [subprocess.Popen([sys.executable, "-c", code], env=dict(env, SHMEM_PE=str(pe)), stdout=subprocess.PIPE,
-                              stderr=subprocess.STDOUT, text=True) for pe in range(npes)]
-    res = []
-    for p in procs:
-        out, _ = p.communicate(timeout=timeout)
-        res.append((p.returncode, out))
-    return res
+    job = launch(npes, [sys.executable, "-c", PRELUDE + textwrap.dedent(body)], gpu=False, timeout=timeout, env=env)
+    return list(zip(job.rc, job.out))
 
 
 @pytest.mark.parametrize("npes", [2, 3, 5])
@@ -118,21 +116,11 @@ def test_identity_from_torchrun_env(tmp_path):
     assert (me, npes) == (int(os.environ['RANK']), 2)
     shm.barrier_all(); shm.finalize()
     """
-    code_env = {"SHMEM_NPES": "", "SHMEM_PE": ""}
-    env = dict(os.environ, SHMEM_BOOTSTRAP_ONLY="1", SHMEM_JOB_ID=uuid.uuid4().hex[:12], WORLD_SIZE="2")
-    env.update(code_env)
-    code = textwrap.dedent(f"""
-        import os, sys
-        sys.path.insert(0, {PKG!r})
-        import shmem_reduce
-        shm = shmem_reduce.Shmem(); shm.init()
-        me, npes = shm.my_pe(), shm.n_pes()
-    """) + textwrap.dedent(body)
-    procs = [subprocess.Popen([sys.executable, "-c", code], env=dict(env, RANK=str(r)), stdout=subprocess.PIPE,
-                              stderr=subprocess.STDOUT, text=True) for r in range(2)]
-    for p in procs:
-        out, _ = p.communicate(timeout=60)
-        assert p.returncode == 0, out
+    env = {"SHMEM_NPES": "", "SHMEM_PE": "", "SHMEM_JOB_ID": uuid.uuid4().hex[:12], "WORLD_SIZE": "2"}
+    job = launch(2, [sys.executable, "-c", PRELUDE + textwrap.dedent(body)], gpu=False, timeout=60, env=env,
+                 per_pe_env={r: {"RANK": str(r)} for r in range(2)}, identity=False)
+    for rc, out in zip(job.rc, job.out):
+        assert rc == 0, out
 
 
 def test_get_put_with_null_buffer_name_it(tmp_path):

@@ -8,6 +8,8 @@ import sys
 
 import pytest
 
+from _pes import oshrun_module
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIBDIR = os.path.join(ROOT, "osss-gasnet_amd", "lib")
 
@@ -54,16 +56,6 @@ def test_c_program_compiles_and_links(tmp_path):
     exe = build(tmp_path)
     out = subprocess.check_output(["nm", "-u", exe], text=True)
     assert "shmem_int_sum_to_all" in out and "shmem_double_max_to_all" in out
-
-
-def oshrun_module():
-    import importlib.machinery
-    import importlib.util
-    loader = importlib.machinery.SourceFileLoader("oshrun", os.path.join(ROOT, "tools", "oshrun"))
-    spec = importlib.util.spec_from_loader("oshrun", loader)
-    mod = importlib.util.module_from_spec(spec)
-    loader.exec_module(mod)
-    return mod
 
 
 def test_oshrun_hardware_queue_policy():

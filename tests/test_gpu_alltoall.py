@@ -17,13 +17,13 @@ import json
 import os
 import subprocess
 import sys
-import uuid
 
 import numpy as np
 import pytest
 
+from _pes import launch
 from alltoall_worker import SENTINEL, source_of
-from test_gpu_multipe import members, oshrun_queues
+from test_gpu_multipe import members
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -95,26 +95,11 @@ def test_strided_pull_offsets_past_4_gib(kernel_results):
 def run_a2a(npes, cases, tmp_path, extra_env=None, timeout=300, offset=0):
     spec = tmp_path / "spec.json"
     spec.write_text(json.dumps({"cases": cases, "offset": offset}))
-    env = dict(os.environ)
-    env.update({"SHMEM_NPES": str(npes), "SHMEM_JOB_ID": uuid.uuid4().hex[:12], "SHMEM_DEVICE": "0",
-                "SHMEM_DEVICE_HEAP_SIZE": "96M", "SHMEM_DEVICE_SCRATCH_SIZE": "384K",
-                "SHMEM_SYMMETRIC_HEAP_SIZE": "64M", "SHMEM_BARRIER_TIMEOUT": "120", "SHMEM_PEER_ACQUIRE": "1"})
-    env.update(oshrun_queues(npes, env))
+    env = {"SHMEM_DEVICE_HEAP_SIZE": "96M", "SHMEM_DEVICE_SCRATCH_SIZE": "384K",
+           "SHMEM_SYMMETRIC_HEAP_SIZE": "64M", "SHMEM_BARRIER_TIMEOUT": "120", "SHMEM_PEER_ACQUIRE": "1"}
     env.update(extra_env or {})
-    procs = [subprocess.Popen([sys.executable, os.path.join(HERE, "alltoall_worker.py"), str(spec), str(tmp_path)],
-                              env=dict(env, SHMEM_PE=str(pe)), stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
-                              text=True) for pe in range(npes)]
-    outs = []
-    for p in procs:
-        try:
-            out, _ = p.communicate(timeout=timeout)
-        except subprocess.TimeoutExpired:
-            for q in procs:
-                q.kill()
-            raise
-        outs.append((p.returncode, out))
-    for pe, (rc, out) in enumerate(outs):
-        assert rc == 0, f"PE {pe} exited {rc}:\n{out[-3000:]}"
+    launch(npes, [sys.executable, os.path.join(HERE, "alltoall_worker.py"), str(spec), str(tmp_path)], gpu=True,
+           timeout=timeout, env=env).ok()
     return [np.load(tmp_path / f"pe{pe}.npz") for pe in range(npes)]
 
 
@@ -339,22 +324,8 @@ def test_fortran_style_caller_two_pes(tmp_path):
 def test_alltoall_tensors_two_pes():
     """Shmem.alltoall_tensors on float32 and int64 tensors against torch
     indexing of the inputs (tests/_alltoall_torch_worker.py)."""
-    env = dict(os.environ, SHMEM_NPES="2", SHMEM_JOB_ID=uuid.uuid4().hex[:12], SHMEM_DEVICE="0",
-               SHMEM_DEVICE_HEAP_SIZE="64M", SHMEM_DEVICE_SCRATCH_SIZE="3M", SHMEM_BARRIER_TIMEOUT="120",
+    env = dict(SHMEM_DEVICE_HEAP_SIZE="64M", SHMEM_DEVICE_SCRATCH_SIZE="3M", SHMEM_BARRIER_TIMEOUT="120",
                SHMEM_PEER_ACQUIRE="1")
-    procs = [subprocess.Popen([sys.executable, os.path.join(HERE, "_alltoall_torch_worker.py")],
-                              env=dict(env, SHMEM_PE=str(pe)), stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
-                              text=True) for pe in range(2)]
-    outs = []
-    for p in procs:
-        try:
-            out, _ = p.communicate(timeout=120)
-        except subprocess.TimeoutExpired:
-            for q in procs:
-                q.kill()
-            raise
-        outs.append(out)
-    for pe, (p, out) in enumerate(zip(procs, outs)):
-        assert p.returncode == 0, f"PE {pe} failed:\n{out[-4000:]}"
-        rec = json.loads([ln for ln in out.splitlines() if ln.startswith("{")][-1])
+    for rec in launch(2, [sys.executable, os.path.join(HERE, "_alltoall_torch_worker.py")], gpu=True, timeout=120,
+                      env=env).records():
         assert rec["ok"] and rec["checked"] == 5, rec

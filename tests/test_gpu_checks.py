@@ -15,12 +15,11 @@ one test GPU.
 * settings that must agree across PEs (SHMEM_REDUCE_ORDER, ...) abort init.
 """
 import os
-import subprocess
 import sys
-import time
-import uuid
 
 import pytest
+
+from _pes import launch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -33,24 +32,11 @@ PRELUDE = ("import sys, os, time\nsys.path[:0] = [%r, %r, %r]\n" % (HERE, os.pat
 
 
 def spawn(npes, code, extra=None, per_pe=None, timeout=120):
-    env = dict(os.environ, SHMEM_NPES=str(npes), SHMEM_JOB_ID=uuid.uuid4().hex[:12], SHMEM_DEVICE="0",
-               SHMEM_DEVICE_HEAP_SIZE="32M", SHMEM_DEVICE_SCRATCH_SIZE="3M", SHMEM_BARRIER_TIMEOUT="120")
+    """exit statuses, outputs and the wall-clock time of the last exit"""
+    env = dict(SHMEM_DEVICE_HEAP_SIZE="32M", SHMEM_DEVICE_SCRATCH_SIZE="3M", SHMEM_BARRIER_TIMEOUT="120")
     env.update(extra or {})
-    procs = []
-    for pe in range(npes):
-        e = dict(env, SHMEM_PE=str(pe))
-        e.update((per_pe or {}).get(pe, {}))
-        procs.append(subprocess.Popen([sys.executable, "-c", PRELUDE + code], env=e, stdout=subprocess.PIPE,
-                                      stderr=subprocess.STDOUT, text=True))
-    outs = []
-    for p in procs:
-        try:
-            outs.append(p.communicate(timeout=timeout)[0])
-        except subprocess.TimeoutExpired:
-            for q in procs:
-                q.kill()
-            raise
-    return [p.returncode for p in procs], outs, time.time()
+    job = launch(npes, [sys.executable, "-c", PRELUDE + code], gpu=True, timeout=timeout, env=env, per_pe_env=per_pe)
+    return job.rc, job.out, job.started + job.elapsed
 
 
 # ---------------------------------------------------------------------------

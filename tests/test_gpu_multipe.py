@@ -16,9 +16,7 @@ process, then checks every PE's target against the oracle:
 import itertools
 import json
 import os
-import subprocess
 import sys
-import uuid
 
 import numpy as np
 import pytest
@@ -26,56 +24,23 @@ import pytest
 import oracle
 from _compare import assert_match
 from _inputs import source
+from _pes import launch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 pytestmark = [pytest.mark.gpu, pytest.mark.multipe]
 
 
-def oshrun_queues(npes, env):
-    """tools/oshrun's hardware-queue policy for PEs sharing one GPU."""
-    import importlib.machinery
-    import importlib.util
-    path = os.path.join(os.path.dirname(HERE), "tools", "oshrun")
-    loader = importlib.machinery.SourceFileLoader("oshrun", path)
-    spec = importlib.util.spec_from_loader("oshrun", loader)
-    mod = importlib.util.module_from_spec(spec)
-    loader.exec_module(mod)
-    return mod.hw_queue_env(npes, True, env)
-
-
 def run_pes(npes, cases, tmp_path, extra_env=None, timeout=600, per_pe_env=None):
     spec = tmp_path / "spec.json"
     spec.write_text(json.dumps({"cases": cases}))
-    env = dict(os.environ)
-    env.update({"SHMEM_NPES": str(npes), "SHMEM_JOB_ID": uuid.uuid4().hex[:12], "SHMEM_DEVICE": "0",
-                "SHMEM_DEVICE_HEAP_SIZE": "96M", "SHMEM_DEVICE_SCRATCH_SIZE": "384K",
-                "SHMEM_BARRIER_TIMEOUT": "120",
-                # the multi-GPU layout queues a system-scope acquire before every read of peers'
-                # buffers (peers on other GPUs); the PEs here share one GPU, so force it on
-                "SHMEM_PEER_ACQUIRE": "1"})
-    # PEs sharing the one test GPU: the job's hardware queues kept at 16, the
-    # same policy as tools/oshrun (8 processes x the default 4 oversubscribe
-    # the GPU's queue slots and every call then waits ~34 ms for a time slice;
-    # DESIGN.md section 5)
-    env.update(oshrun_queues(npes, env))
+    env = {"SHMEM_DEVICE_HEAP_SIZE": "96M", "SHMEM_DEVICE_SCRATCH_SIZE": "384K",
+           "SHMEM_BARRIER_TIMEOUT": "120",
+           # the multi-GPU layout queues a system-scope acquire before every read of peers'
+           # buffers (peers on other GPUs); the PEs here share one GPU, so force it on
+           "SHMEM_PEER_ACQUIRE": "1"}
     env.update(extra_env or {})
-    procs = []
-    for pe in range(npes):
-        e = dict(env, SHMEM_PE=str(pe))
-        e.update((per_pe_env or {}).get(pe, {}))
-        procs.append(subprocess.Popen([sys.executable, os.path.join(HERE, "pe_worker.py"), str(spec), str(tmp_path)],
-                                      env=e, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True))
-    outs = []
-    for p in procs:
-        try:
-            out, _ = p.communicate(timeout=timeout)
-        except subprocess.TimeoutExpired:
-            for q in procs:
-                q.kill()
-            raise
-        outs.append((p.returncode, out))
-    for pe, (rc, out) in enumerate(outs):
-        assert rc == 0, f"PE {pe} exited {rc}:\n{out[-3000:]}"
+    launch(npes, [sys.executable, os.path.join(HERE, "pe_worker.py"), str(spec), str(tmp_path)], gpu=True,
+           timeout=timeout, env=env, per_pe_env=per_pe_env).ok()
     return [np.load(tmp_path / f"pe{pe}.npz") for pe in range(npes)]
 
 
@@ -394,17 +359,8 @@ def test_fortran_binding_three_pes(tmp_path):
 
 def test_bad_active_set_aborts_every_pe(tmp_path):
     """A PE outside the active set fails loudly and its peers do not hang."""
-    cases = [{"id": 0, "op": "sum", "dtype": "double", "n": 10, "sets": [[0, 0, 2]], "mode": "dev",
-              "algorithm": "p2p", "seed": 1},
-             # PE 1 calls with a set that excludes it -> fatal; PE 0 waits in a barrier
-             {"id": 1, "op": "sum", "dtype": "double", "n": 10, "sets": [[0, 0, 1], [1, 0, 1]], "mode": "dev",
-              "algorithm": "p2p", "seed": 2, "bad_for_pe1": True}]
-    spec = tmp_path / "spec.json"
-    bad = dict(cases[1])
-    bad["sets"] = [[0, 0, 2]]
-    spec.write_text(json.dumps({"cases": [cases[0], bad]}))
-    env = dict(os.environ, SHMEM_NPES="2", SHMEM_JOB_ID=uuid.uuid4().hex[:12], SHMEM_DEVICE="0",
-               SHMEM_DEVICE_HEAP_SIZE="32M", SHMEM_DEVICE_SCRATCH_SIZE="384K", SHMEM_BARRIER_TIMEOUT="60")
+    # PE 1 calls with a set that excludes it -> fatal; PE 0 waits in a barrier
+    env = dict(SHMEM_DEVICE_HEAP_SIZE="32M", SHMEM_DEVICE_SCRATCH_SIZE="384K", SHMEM_BARRIER_TIMEOUT="60")
     code = ("import sys,os; sys.path[:0]=[%r,%r,%r]\n" % (HERE, os.path.join(os.path.dirname(HERE), "osss-gasnet_amd"),
                                                           os.path.join(os.path.dirname(HERE), "oracle")) +
             "import shmem_reduce\nshm=shmem_reduce.Shmem(); shm.init(); d=shm.malloc_device(1024)\n"
@@ -412,11 +368,9 @@ def test_bad_active_set_aborts_every_pe(tmp_path):
             "shm.to_all('sum','double',d,d,10,0,0,2)\n"
             "if pe==1: shm.to_all('sum','double',d,d,10,0,0,1)\n"
             "else: shm.to_all('sum','double',d,d,10,0,0,2)\n")
-    procs = [subprocess.Popen([sys.executable, "-c", code], env=dict(env, SHMEM_PE=str(pe)),
-                              stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True) for pe in range(2)]
-    outs = [p.communicate(timeout=120) for p in procs]
-    assert procs[1].returncode != 0 and "not in the active set" in outs[1][0]
-    assert procs[0].returncode != 0 and "aborting" in outs[0][0]
+    job = launch(2, [sys.executable, "-c", code], gpu=True, timeout=120, env=env)
+    assert job.rc[1] != 0 and "not in the active set" in job.out[1]
+    assert job.rc[0] != 0 and "aborting" in job.out[0]
 
 
 def test_rccl_init_is_bounded_on_a_shared_gpu(tmp_path):
@@ -425,8 +379,7 @@ def test_rccl_init_is_bounded_on_a_shared_gpu(tmp_path):
     (ready or not, the same answer) instead of hanging or aborting the job, and
     the P2P schedule must still work afterwards. bench.py relies on this before
     timing its RCCL comparison leg."""
-    env = dict(os.environ, SHMEM_NPES="2", SHMEM_JOB_ID=uuid.uuid4().hex[:12], SHMEM_DEVICE="0",
-               SHMEM_DEVICE_HEAP_SIZE="32M", SHMEM_DEVICE_SCRATCH_SIZE="384K", SHMEM_BARRIER_TIMEOUT="60")
+    env = dict(SHMEM_DEVICE_HEAP_SIZE="32M", SHMEM_DEVICE_SCRATCH_SIZE="384K", SHMEM_BARRIER_TIMEOUT="60")
     code = ("import sys,os,time; sys.path[:0]=[%r,%r]\n" % (HERE, os.path.join(os.path.dirname(HERE), "osss-gasnet_amd")) +
             "import numpy as np, shmem_reduce\nshm=shmem_reduce.Shmem(); shm.init()\n"
             "t0=time.time(); rc=shm.lib.shmemx_rccl_init(15.0); dt=time.time()-t0\n"
@@ -434,14 +387,12 @@ def test_rccl_init_is_bounded_on_a_shared_gpu(tmp_path):
             "shm.to_all('sum','double',d,d,16,0,0,2)\n"
             "ok=(shm.get(d,16,'double')==3.0).all()\n"
             "print('rc', rc, 'dt %.1f' % dt, 'p2p', ok, flush=True)\nshm.finalize()\n")
-    procs = [subprocess.Popen([sys.executable, "-c", code], env=dict(env, SHMEM_PE=str(pe)),
-                              stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True) for pe in range(2)]
-    outs = [p.communicate(timeout=100)[0] for p in procs]
-    for p, out in zip(procs, outs):
-        assert p.returncode == 0, out[-2000:]
+    job = launch(2, [sys.executable, "-c", code], gpu=True, timeout=100, env=env)
+    for rc, out in zip(job.rc, job.out):
+        assert rc == 0, out[-2000:]
         assert "p2p True" in out, out[-2000:]
-    rcs = [int(o.split("rc ")[1].split()[0]) for o in outs]
-    assert rcs[0] == rcs[1], outs
+    rcs = [int(o.split("rc ")[1].split()[0]) for o in job.out]
+    assert rcs[0] == rcs[1], job.out
 
 
 def test_small_host_arrays_one_launch_and_mixed(tmp_path):
@@ -786,8 +737,7 @@ def test_peer_heap_mapping_failure_other_pairs_abort_cleanly(tmp_path):
     must end the job with the library's message on every PE -- no PE may take
     a kernel path that reads a peer's heap."""
     for n, mode in ((16, "dev"), (16, "host"), (300000, "dev")):
-        env = dict(os.environ, SHMEM_NPES="3", SHMEM_JOB_ID=uuid.uuid4().hex[:12], SHMEM_DEVICE="0",
-                   SHMEM_DEVICE_HEAP_SIZE="32M", SHMEM_DEVICE_SCRATCH_SIZE="3M", SHMEM_BARRIER_TIMEOUT="60",
+        env = dict(SHMEM_DEVICE_HEAP_SIZE="32M", SHMEM_DEVICE_SCRATCH_SIZE="3M", SHMEM_BARRIER_TIMEOUT="60",
                    SHMEM_TEST_IPC_FAIL="heap", NCCL_SOCKET_IFNAME="lo", NCCL_IB_DISABLE="1")
         code = ("import sys,os; sys.path[:0]=[%r,%r]\n" % (HERE, os.path.join(os.path.dirname(HERE), "osss-gasnet_amd")) +
                 "import numpy as np, shmem_reduce\nshm=shmem_reduce.Shmem(); shm.init()\n"
@@ -795,10 +745,8 @@ def test_peer_heap_mapping_failure_other_pairs_abort_cleanly(tmp_path):
                 + ("d=shm.malloc_device(8*n); s=d\n" if mode == "dev" else
                    "a=np.ones(n,dtype=np.int32); d=a.ctypes.data; s=d\n") +
                 "shm.to_all('xor','int',d,s,n,0,0,3)\nprint('CALL-RETURNED', flush=True)\nshm.finalize()\n")
-        procs = [subprocess.Popen([sys.executable, "-c", code],
-                                  env=dict(env, SHMEM_PE=str(pe), NCCL_HOSTID=f"shmem-rccl-test-pe{pe}"),
-                                  stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True) for pe in range(3)]
-        outs = [p.communicate(timeout=120)[0] for p in procs]
-        for p, out in zip(procs, outs):
-            assert p.returncode != 0 and "CALL-RETURNED" not in out, out[-2000:]
-        assert any("only the RCCL pairs" in o for o in outs), outs
+        job = launch(3, [sys.executable, "-c", code], gpu=True, timeout=120, env=env,
+                     per_pe_env={pe: {"NCCL_HOSTID": f"shmem-rccl-test-pe{pe}"} for pe in range(3)})
+        for rc, out in zip(job.rc, job.out):
+            assert rc != 0 and "CALL-RETURNED" not in out, out[-2000:]
+        assert any("only the RCCL pairs" in o for o in job.out), job.out

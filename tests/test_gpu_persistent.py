@@ -9,45 +9,24 @@ another op, a broadcast, a stream-ordered call); gaps longer than its idle
 time; gaps around the idle time (a call rung as the server leaves); a call
 after GPU work the caller queued and then completed (it sees that work's
 result)."""
-import json
 import os
-import subprocess
 import sys
-import uuid
 
 import pytest
 
-from test_gpu_multipe import oshrun_queues
+from _pes import launch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 pytestmark = [pytest.mark.gpu, pytest.mark.multipe]
 
 
 def run(npes, script, seed=1, extra=None, timeout=300):
-    env = dict(os.environ)
-    env.update({"SHMEM_NPES": str(npes), "SHMEM_JOB_ID": uuid.uuid4().hex[:12], "SHMEM_DEVICE": "0",
-                "SHMEM_DEVICE_HEAP_SIZE": "32M", "SHMEM_DEVICE_SCRATCH_SIZE": "384K",
-                "SHMEM_DEVICE_ORDER_SIZE": "4M", "SHMEM_BARRIER_TIMEOUT": "60", "SHMEM_PEER_ACQUIRE": "1",
-                "SHMEM_PERSISTENT": "1"})
-    env.update(oshrun_queues(npes, env))
+    env = {"SHMEM_DEVICE_HEAP_SIZE": "32M", "SHMEM_DEVICE_SCRATCH_SIZE": "384K",
+           "SHMEM_DEVICE_ORDER_SIZE": "4M", "SHMEM_BARRIER_TIMEOUT": "60", "SHMEM_PEER_ACQUIRE": "1",
+           "SHMEM_PERSISTENT": "1"}
     env.update(extra or {})
-    procs = [subprocess.Popen([sys.executable, os.path.join(HERE, "persistent_worker.py"), script, str(seed)],
-                              env=dict(env, SHMEM_PE=str(pe)), stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
-                              text=True) for pe in range(npes)]
-    outs = []
-    for p in procs:
-        try:
-            out, _ = p.communicate(timeout=timeout)
-        except subprocess.TimeoutExpired:
-            for q in procs:
-                q.kill()
-            raise
-        outs.append((p.returncode, out))
-    stats = []
-    for pe, (rc, out) in enumerate(outs):
-        assert rc == 0, f"PE {pe} exited {rc}:\n{out[-3000:]}"
-        stats.append(json.loads([ln for ln in out.splitlines() if ln.startswith("{")][-1]))
-    return stats
+    return launch(npes, [sys.executable, os.path.join(HERE, "persistent_worker.py"), script, str(seed)], gpu=True,
+                  timeout=timeout, env=env).records()
 
 
 @pytest.mark.parametrize("npes", [1, 2, 3])

@@ -15,7 +15,7 @@ import uuid
 import pytest
 
 import _scan_ref as S
-from test_gpu_multipe import oshrun_queues
+from _pes import launch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -28,30 +28,13 @@ EIGHT_TYPES = ("double", "float", "int", "longlong", "longdouble", "complexf", "
 def run_pes(npes, cases, tmp_path, extra_env=None, timeout=300):
     spec = tmp_path / f"spec_{uuid.uuid4().hex[:6]}.json"
     spec.write_text(json.dumps({"cases": cases}))
-    env = dict(os.environ)
-    env.update({"SHMEM_NPES": str(npes), "SHMEM_JOB_ID": uuid.uuid4().hex[:12], "SHMEM_DEVICE": "0",
-                "SHMEM_DEVICE_HEAP_SIZE": "96M", "SHMEM_DEVICE_SCRATCH_SIZE": "384K",
-                "SHMEM_SYMMETRIC_HEAP_SIZE": "64M", "SHMEM_BARRIER_TIMEOUT": "120", "SHMEM_PEER_ACQUIRE": "1"})
-    env.update(oshrun_queues(npes, env))
+    env = {"SHMEM_DEVICE_HEAP_SIZE": "96M", "SHMEM_DEVICE_SCRATCH_SIZE": "384K",
+           "SHMEM_SYMMETRIC_HEAP_SIZE": "64M", "SHMEM_BARRIER_TIMEOUT": "120", "SHMEM_PEER_ACQUIRE": "1"}
     env.update(extra_env or {})
-    procs = [subprocess.Popen([sys.executable, os.path.join(HERE, "_scan_worker.py"), str(spec)],
-                              env=dict(env, SHMEM_PE=str(pe)), stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
-                              text=True) for pe in range(npes)]
-    outs = []
-    for p in procs:
-        try:
-            out, _ = p.communicate(timeout=timeout)
-        except subprocess.TimeoutExpired:
-            for q in procs:
-                q.kill()
-            raise
-        outs.append((p.returncode, out))
-    recs = []
-    for pe, (rc, out) in enumerate(outs):
-        assert rc == 0, f"PE {pe} exited {rc}:\n{out[-3000:]}"
-        rec = json.loads([ln for ln in out.splitlines() if ln.startswith("{")][-1])
+    recs = launch(npes, [sys.executable, os.path.join(HERE, "_scan_worker.py"), str(spec)], gpu=True,
+                  timeout=timeout, env=env).records()
+    for rec in recs:
         assert rec["checked"] == len(cases) and not rec["failures"], rec
-        recs.append(rec)
     return recs
 
 

@@ -2,37 +2,21 @@
 GPU): the members map each other's caching-allocator segments for the call
 (extmap.c) -- no staging copies -- and every PE gets the reference's result
 for itself; a view off 16-byte alignment makes every member stage instead."""
-import json
 import os
-import subprocess
 import sys
-import uuid
 
 import pytest
+
+from _pes import launch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 pytestmark = [pytest.mark.gpu, pytest.mark.multipe]
 
 
 def run_workers(script, npes=2):
-    env = dict(os.environ, SHMEM_NPES=str(npes), SHMEM_JOB_ID=uuid.uuid4().hex[:12], SHMEM_DEVICE="0",
-               SHMEM_DEVICE_HEAP_SIZE="64M", SHMEM_DEVICE_SCRATCH_SIZE="3M", SHMEM_BARRIER_TIMEOUT="120",
+    env = dict(SHMEM_DEVICE_HEAP_SIZE="64M", SHMEM_DEVICE_SCRATCH_SIZE="3M", SHMEM_BARRIER_TIMEOUT="120",
                SHMEM_PEER_ACQUIRE="1")
-    procs = [subprocess.Popen([sys.executable, os.path.join(HERE, script)],
-                              env=dict(env, SHMEM_PE=str(pe)), stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
-                              text=True) for pe in range(npes)]
-    outs = []
-    for p in procs:
-        try:
-            out, _ = p.communicate(timeout=300)
-        except subprocess.TimeoutExpired:
-            for q in procs:
-                q.kill()
-            raise
-        outs.append(out)
-    for pe, (p, out) in enumerate(zip(procs, outs)):
-        assert p.returncode == 0, f"PE {pe} failed:\n{out[-4000:]}"
-    return [json.loads([ln for ln in out.splitlines() if ln.startswith("{")][-1]) for out in outs]
+    return launch(npes, [sys.executable, os.path.join(HERE, script)], gpu=True, timeout=300, env=env).records()
 
 
 def test_torch_tensors_mapped_between_pes():
