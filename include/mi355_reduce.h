@@ -230,8 +230,13 @@ int mi355_kernel_name (const void *kernel, char *buf, size_t len);
  * layer's launchers count them when they cap a grid (256 when the device
  * cannot be queried). mi355_last_launch_grid: the grid (blocks in x and y) of
  * the kernel this layer launched last from the calling thread through its
- * launch helper -- every fold, copy, patch copy and strided pull; 0, 0 before
- * the first. Read-only, never used by the library itself. */
+ * launch helper, the same launch mi355_last_kernel names -- every fold, copy,
+ * patch copy, strided pull, atomic and prefix fold, the signal-only kernel,
+ * mi355_fused_allreduce, mi355_fused_pull and mi355_fused_server; 0, 0 before
+ * the first. Never recorded, by either: mi355_device_barrier,
+ * mi355_acquire_system, mi355_convert_short and the self-test kernels
+ * (mi355_poke, the mi355_peek family, mi355_mark_plain, mi355_producer_read).
+ * Read-only, never used by the library itself. */
 int mi355_device_cus (void);
 void mi355_last_launch_grid (unsigned *gx, unsigned *gy);
 

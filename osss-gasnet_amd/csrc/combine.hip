@@ -347,7 +347,7 @@ static int copy_segments_impl(void *const *dsts, const void *const *srcs, const 
 static int combine_orders_impl(int op, int dtype, void *const *dsts, const void *const *srcs, int nsrc, size_t n,
                                void *stream);
 
-// Every entry point returns through LaunchState::end_call (combine_kernels.h): what each consumes and cancels.
+// Every entry point returns through LaunchState::end_call (launch.h): what each consumes and cancels.
 extern "C" int mi355_combine(int op, int dtype, void *dst, const void *const *srcs, int nsrc,
                              size_t n, void *stream) {
     return t_launch.end_call(combine_impl(op, dtype, dst, srcs, nsrc, n, stream), ARMED_NAN, ARMED_DIR);
@@ -607,17 +607,6 @@ extern "C" void mi355_time_next_launch(void *start_event, void *stop_event) {
     t_launch.ev_start = (hipEvent_t)start_event;
     t_launch.ev_stop = (hipEvent_t)stop_event;
 }
-
-// For fused.hip (same library): take the event pair armed for the next
-// launch, if any, so its kernels carry the stamps too.
-extern "C" void mi355i_take_launch_events(void **start_event, void **stop_event) {
-    *start_event = t_launch.ev_start;
-    *stop_event = t_launch.ev_stop;
-    t_launch.ev_start = t_launch.ev_stop = nullptr;
-}
-
-// For fused.hip: its launches count as this layer's last kernel too.
-extern "C" void mi355i_note_launch(const void *kernel) { t_launch.last_kernel = kernel; }
 
 extern "C" const void *mi355_last_kernel(void) { return t_launch.last_kernel; }
 

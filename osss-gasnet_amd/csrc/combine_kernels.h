@@ -4,16 +4,12 @@
 // 8 x 7 x 8 instantiations compile in parallel) and combine.hip (the C ABI,
 // the copy and signal kernels). See combine.hip for the design notes.
 #pragma once
-#include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <atomic>
-#include <mutex>
 #include <type_traits>
-#include <utility>
 
-#include "launch_plan.h"
+#include "launch.h"
 #include "mi355_reduce.h"
 #include "ops.h"
 
@@ -21,23 +17,12 @@ namespace mi355k {
 
 using namespace mi355;
 
-constexpr int kBlock = 256;
 constexpr int kMaxSrc = 8;
 
 // ---------------------------------------------------------------------------
 // kernels
 // ---------------------------------------------------------------------------
-// Completion signal (mi355_signal_next_launch): the last block to finish
-// stores `epoch` into a host-visible word, so the host learns the result is
-// in memory ~4 us sooner than through hipStreamSynchronize (tools/probes/latency.hip:
-// 6.9 vs 10.7 us for a launch round trip on MI355X).
-struct Signal {
-    unsigned *count;  // device word, 0 between launches (the last block resets it)
-    unsigned *flag;   // host-coherent word the host spins on; nullptr = no signal
-    unsigned epoch;
-};
-
-// Publish recipe of MI355X_MICROARCH.md (inter-workgroup visibility, valid
+// The completion signal (launch.h, Signal), on the device. Publish recipe of MI355X_MICROARCH.md (inter-workgroup visibility, valid
 // form "sc1 payload + drained waves + flag"): the bulk stores are
 // write-through (`nt sc1` st16 in the copy, `sc1` st16_fold in the folds), so
 // once every wave has drained its stores they are in memory for any agent; a
@@ -554,145 +539,9 @@ __global__ __launch_bounds__(kBlock) void combine_orders_scalar(OrdersParams p) 
 }
 
 // ---------------------------------------------------------------------------
-// launch helpers
+// launch shapes and launchers (the launch itself, the armed state and the
+// grid caps: launch.h)
 // ---------------------------------------------------------------------------
-inline int g_cus[64];
-
-// What a caller armed for this thread's next launch, and what this thread
-// launched last: the one owner of that state. Who takes what:
-//   launch()              the event pair, always; the signal when the launch
-//                         is the call's `final` one (earlier launches of a
-//                         multi-launch call run unsignalled); it records the
-//                         kernel and grid. fused.hip's launches reach the
-//                         events and the record through mi355i_take_launch_events
-//                         and mi355i_note_launch only.
-//   launch_fixed()        the NaN words, before anything else: the k-source
-//                         fold is the only kernel that carries them
-//   next_copy_descends()  the direction pin (combine.hip: single-segment copies)
-//   fire_on_host()        a call with nothing to launch fires the signal from
-//                         the host and takes it; the events stay armed for the
-//                         next launch
-//   end_call()            every entry point returns through it: `spent` names
-//                         what the entry consumes even when it launched
-//                         nothing or another kernel than the one that carries
-//                         it; an error return also cancels the signal, the
-//                         events and `on_error` (nothing will carry them).
-//                         mi355_combine: the NaN words spent, the pin dropped
-//                         on error; mi355_combine_orders: the pin dropped on
-//                         error; mi355_copy_segments: the pin spent (a
-//                         multi-segment launch always ascends);
-//                         mi355_nan_patch_copy and the strided copies: neither.
-enum { ARMED_NAN = 1, ARMED_DIR = 2 };
-struct LaunchState {
-    Signal sig = {nullptr, nullptr, 0};                  // mi355_signal_next_launch
-    hipEvent_t ev_start = nullptr, ev_stop = nullptr;    // mi355_time_next_launch
-    unsigned long long *nan_set = nullptr, *nan_clear = nullptr;   // mi355_nan_flag_next_launch
-    int copy_dir = 0;   // mi355_copy_direction_next_launch: > 0 ascending, < 0 descending, 0: none
-    const void *last_kernel = nullptr;   // host stub of the kernel launched last (mi355_last_kernel)
-    unsigned last_grid[2] = {0, 0};      // ... and its grid (mi355_last_launch_grid)
-
-    int end_call(int rc, unsigned spent = 0, unsigned on_error = 0) {
-        if (rc != 0) {
-            sig = Signal{nullptr, nullptr, 0};
-            ev_start = ev_stop = nullptr;
-            spent |= on_error;
-        }
-        if (spent & ARMED_NAN) nan_set = nan_clear = nullptr;
-        if (spent & ARMED_DIR) copy_dir = 0;
-        return rc;
-    }
-};
-inline thread_local LaunchState t_launch;
-
-// A host-visible word the host can also write: an armed signal that no kernel
-// will carry (nothing to launch) is fired right here, in stream order.
-inline void fire_on_host(hipStream_t st) {
-    Signal &sig = t_launch.sig;
-    if (sig.flag == nullptr) return;
-    if (hipStreamSynchronize(st) == hipSuccess) __atomic_store_n(sig.flag, sig.epoch, __ATOMIC_RELEASE);
-    sig = Signal{nullptr, nullptr, 0};
-}
-
-// `final`: the last launch of an API call, the one that carries the signal;
-// `block`: threads per block (amo.hip's one-wave kernel: 64)
-template <typename K, typename P>
-int launch(K kernel, dim3 grid, hipStream_t st, P p, bool final = true, unsigned block = kBlock) {
-    LaunchState &s = t_launch;
-    p.sig = Signal{nullptr, nullptr, 0};
-    if (final) {
-        p.sig = s.sig;
-        s.sig = Signal{nullptr, nullptr, 0};
-    }
-    s.last_kernel = (const void *)kernel;
-    s.last_grid[0] = grid.x, s.last_grid[1] = grid.y;
-    if (s.ev_start != nullptr || s.ev_stop != nullptr) {
-        hipExtLaunchKernelGGL(kernel, grid, dim3(block), 0, st, s.ev_start, s.ev_stop, 0, p);
-        s.ev_start = s.ev_stop = nullptr;
-    } else {
-        hipLaunchKernelGGL(kernel, grid, dim3(block), 0, st, p);
-    }
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
-}
-
-inline int device_cus() {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-    if (g_cus[dev] == 0) {
-        int cus = 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-            cus <= 0)
-            cus = 256;
-        g_cus[dev] = cus;
-    }
-    return g_cus[dev];
-}
-
-// Blocks for a streaming launch: enough to cover the work once, capped at
-// kBlocksPerCU resident blocks per CU (grid-stride covers the rest).
-constexpr int kBlocksPerCU = 8;
-
-// Blocks of `fn` one CU holds at once (occupancy API, cached per kernel).
-// A grid-stride launch larger than what is resident runs in rounds, the last
-// one partly empty. The VALU-bound x87 folds cap their grids at this (the
-// every-member x87 sum at 8 sources: 80 VGPRs, 6 blocks per CU instead of
-// the 8 asked: 271 -> 263 us at 8 x 32 MiB, profiles/r03/orders_grid_cap.jsonl).
-// The HBM-bound folds do not: capped at their residency (the 8-source fold
-// holds 152 VGPRs, 3 blocks per CU) they ran 1-4 % slower -- the queued
-// blocks refill CUs as others finish.
-// Several host threads may launch folds (the launch state is per thread):
-// readers see an entry only once its key and value are written (release /
-// acquire on `used`), writers append under a mutex.
-inline int resident_blocks(const void *fn) {
-    static const void *keys[512];
-    static int vals[512];
-    static std::atomic<int> used{0};
-    static std::mutex mu;
-    const int seen = used.load(std::memory_order_acquire);
-    for (int i = 0; i < seen; ++i)
-        if (keys[i] == fn) return vals[i];
-    int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, kBlock, 0) != hipSuccess || n < 1) n = 1;
-    (void)hipGetLastError();
-    std::lock_guard<std::mutex> lock(mu);
-    const int u = used.load(std::memory_order_relaxed);
-    for (int i = seen; i < u; ++i)
-        if (keys[i] == fn) return vals[i];  // another thread added it meanwhile
-    if (u < 512) {
-        keys[u] = fn;
-        vals[u] = n;
-        used.store(u + 1, std::memory_order_release);
-    }
-    return n;
-}
-
-inline unsigned grid_for(uint64_t units_per_block_pass, uint64_t units, int blocks_per_cu = kBlocksPerCU) {
-    uint64_t want = (units + units_per_block_pass - 1) / units_per_block_pass;
-    uint64_t cap = (uint64_t)device_cus() * blocks_per_cu;
-    if (want < 1) want = 1;
-    return (unsigned)(want < cap ? want : cap);
-}
-
 // Launch shape per source count, from tools/probes/hbm_sweep.hip and
 // tools/probes/fold_bench.py on MI355X (256 MiB per source, double sums,
 // non-temporal loads + `nt sc1` stores at the time; the folds store `sc1`
@@ -769,22 +618,6 @@ template <int OP, int NSRC, typename T> struct OrdersShape {
                                                    : S::blocks_per_cu;
     static constexpr int policy = POL_NT_LOAD;
 };
-
-// A run-time v in [Lo, Hi] as a compile-time constant: f(std::integral_constant<int, v>),
-// MI355_E_INVAL outside the range. One instantiation of f per value. Compared
-// from Hi down: the compiler then emits the kernels those instantiations name
-// in ascending order, as the switch ladders this replaces did, which keeps
-// each translation unit's device code byte for byte what it was.
-template <int Hi, typename F, int... I>
-int with_constant(int v, F &&f, std::integer_sequence<int, I...>) {
-    int rc = MI355_E_INVAL;
-    (void)((v == Hi - I && (rc = f(std::integral_constant<int, Hi - I>{}), true)) || ...);
-    return rc;
-}
-template <int Lo, int Hi, typename F>
-int with_constant(int v, F &&f) {
-    return with_constant<Hi>(v, f, std::make_integer_sequence<int, Hi - Lo + 1>{});
-}
 
 // The plan (launch_plan.h) into a params struct: the vector counts, and every
 // pointer advanced past the head (a null output stays null).

@@ -38,21 +38,20 @@
 // All blocks of the grid must be co-resident (they wait on each other's last
 // block), also beside the grids of other PEs sharing this GPU: the grid is
 // capped by the kernel's occupancy and the number of such PEs
-// (coresident_grid; at most MI355_FUSED_MAX_BLOCKS, one block per CU).
+// (launch.h, coresident_grid; at most MI355_FUSED_MAX_BLOCKS, one block per CU).
 // Every wait is bounded by p.timeout_ticks of the 100 MHz real-time counter.
-#include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <type_traits>
 
+#include "launch.h"
 #include "ops.h"
-#include "residency.h"
 
 namespace {
 
 using namespace mi355;
+using namespace mi355k;  // launch.h: kBlock, launch_recorded, coresident_grid, with_constant
 
-constexpr int kBlock = 256;
 constexpr int kBatch = 8;  // members' vectors in flight per lane in the fold
 
 // Probe build only (csrc/Makefile `probe`, tools/fused_phases.py): the real-time
@@ -728,119 +727,60 @@ __global__ __launch_bounds__(64) void device_barrier(MI355FusedArgs a) {
     finish(a, mine, cnt, ok, a.epoch);
 }
 
-extern "C" void mi355i_take_launch_events(void **start_event, void **stop_event);  // combine.hip
-extern "C" void mi355i_note_launch(const void *kernel);                           // combine.hip
-
-// Launch, carrying the event pair armed by mi355_time_next_launch (if any)
-// as hipExtLaunchKernel stamps: no marker packets on the stream.
-template <typename K, typename P>
-void launch_stamped(K kernel, unsigned grid, unsigned block, hipStream_t st, const P &p) {
-    void *e0 = nullptr, *e1 = nullptr;
-    mi355i_take_launch_events(&e0, &e1);
-    mi355i_note_launch((const void *)kernel);
-    if (e0 != nullptr || e1 != nullptr)
-        hipExtLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, st, (hipEvent_t)e0, (hipEvent_t)e1, 0, p);
-    else
-        hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, st, p);
+// (op, dtype) at run time -> f(std::integral_constant<int, OP>, T{}): the one
+// dispatch of the launched kernel and the server. MI355_E_UNSUP for a pair
+// without an operator (valid_pair), MI355_E_INVAL for an op or dtype outside
+// the fused kernels' -- the 16-bit floats among them.
+template <typename T, typename F>
+int with_op(int op, F &&f) {
+    return with_constant<0, MI355_NUM_OPS - 1>(op, [&](auto o) -> int {
+        if constexpr (valid_pair<decltype(o)::value, T>()) return f(o, T{});
+        else return MI355_E_UNSUP;
+    });
 }
-
-// Co-residency: every block of these grids waits for the grid's last block
-// and for the other members, so all blocks of every such grid running on this
-// GPU at once must be resident together. A launch is capped at the kernel's
-// resident blocks per CU x CUs, divided among the `share` processes that may
-// run such grids here at the same time. Resident blocks per CU: the occupancy
-// query, but at most MI355_FUSED_RESIDENT_PER_CU (residency.h) -- 256-thread
-// blocks are admitted per CU up to floor(800 / (ceil(sgpr / 16) * 16 + 16))
-// (MI355X_MICROARCH.md "Residency"), which the query ignores (at 103-106
-// SGPRs: 6 per CU where the query says 8; 9 PEs x 174 blocks on one GPU never
-// all started) -- and one fewer as a margin. The build checks every such
-// kernel's SGPR/VGPR/LDS use against the constant (tools/check_residency.py).
-struct OccEntry {
-    const void *fn;
-    int blocks_per_cu;
-};
-OccEntry g_occ[256];
-int g_nocc = 0;
-int g_cus = 0;
-
-unsigned coresident_grid(const void *fn, uint64_t want, int share) {
-    if (g_cus == 0) {
-        int dev = 0, cus = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-            cus = 256;
-        g_cus = cus;
-    }
-    int per_cu = -1;
-    for (int i = 0; i < g_nocc; ++i)
-        if (g_occ[i].fn == fn) per_cu = g_occ[i].blocks_per_cu;
-    if (per_cu < 0) {
-        int n = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, kBlock, 0) != hipSuccess || n < 1) n = 1;
-        (void)hipGetLastError();
-        if (n > MI355_FUSED_RESIDENT_PER_CU) n = MI355_FUSED_RESIDENT_PER_CU;
-        per_cu = n > 1 ? n - 1 : 1;
-        if (g_nocc < 256) g_occ[g_nocc++] = OccEntry{fn, per_cu};
-    }
-    uint64_t cap = (uint64_t)per_cu * (uint64_t)g_cus / (uint64_t)(share > 1 ? share : 1);
-    if (cap < 1) cap = 1;
-    if (want > cap) want = cap;
-    return (unsigned)(want < 1 ? 1 : want);
-}
-
-template <typename T>
-int launch_op(const MI355FusedArgs &a, unsigned grid, hipStream_t st) {
-    switch (a.op) {
-#define CASE(O)                                                                        \
-    case O:                                                                            \
-        if constexpr (valid_pair<O, T>()) {                                           \
-            auto k = fused_allreduce<O, T>;                                            \
-            launch_stamped(k, coresident_grid((const void *)k, grid, a.share), kBlock, st, a); \
-            break;                                                                     \
-        } else {                                                                       \
-            return MI355_E_UNSUP;                                                      \
-        }
-        CASE(MI355_OP_SUM)
-        CASE(MI355_OP_PROD)
-        CASE(MI355_OP_AND)
-        CASE(MI355_OP_OR)
-        CASE(MI355_OP_XOR)
-        CASE(MI355_OP_MIN)
-        CASE(MI355_OP_MAX)
-#undef CASE
+template <typename F>
+int with_op_and_type(int op, int dtype, F &&f) {
+    switch (dtype) {
+    case MI355_SHORT: return with_op<int16_t>(op, f);
+    case MI355_INT: return with_op<int32_t>(op, f);
+    case MI355_LONG:
+    case MI355_LONGLONG: return with_op<int64_t>(op, f);
+    case MI355_FLOAT: return with_op<float>(op, f);
+    case MI355_DOUBLE: return with_op<double>(op, f);
+    case MI355_LONGDOUBLE: return with_op<x80>(op, f);
+    case MI355_COMPLEXF: return with_op<cplxf>(op, f);
+    case MI355_COMPLEXD: return with_op<cplxd>(op, f);
     default: return MI355_E_INVAL;
     }
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
 }
 
-template <typename T>
-int launch_server(const MI355FusedArgs &a, MI355ServerMailbox *mb, unsigned first_seq, unsigned long long idle_ticks,
-                  unsigned grid, hipStream_t st) {
-    switch (a.op) {
-#define CASE(O)                                                                                          \
-    case O:                                                                                              \
-        if constexpr (valid_pair<O, T>()) {                                                             \
-            auto k = fused_server<O, T>;                                                                 \
-            mi355i_note_launch((const void *)k);                                                         \
-            hipLaunchKernelGGL(k, dim3(coresident_grid((const void *)k, grid, a.share)), dim3(kBlock), 0, st, a, mb, \
-                               first_seq, idle_ticks);                                                   \
-            break;                                                                                       \
-        } else {                                                                                         \
-            return MI355_E_UNSUP;                                                                        \
-        }
-        CASE(MI355_OP_SUM)
-        CASE(MI355_OP_PROD)
-        CASE(MI355_OP_AND)
-        CASE(MI355_OP_OR)
-        CASE(MI355_OP_XOR)
-        CASE(MI355_OP_MIN)
-        CASE(MI355_OP_MAX)
-#undef CASE
-    default: return MI355_E_INVAL;
+// The member table: min_members to MI355_FUSED_MAX_MEMBERS of them, this PE
+// one of them, each with its signal region and a PE number the region has
+// slots for.
+bool members_ok(const MI355FusedArgs &a, int min_members) {
+    if (a.nmembers < min_members || a.nmembers > MI355_FUSED_MAX_MEMBERS || a.me < 0 || a.me >= a.nmembers)
+        return false;
+    for (int i = 0; i < a.nmembers; ++i)
+        if (a.sig[i] == nullptr || a.pe[i] < 0 || a.pe[i] >= MI355_SIG_RSDONE) return false;
+    return true;
+}
+
+// Every member's source and target (and, need_versions, version area): set
+// and 16-byte aligned. After members_ok.
+bool buffers_ok(const MI355FusedArgs &a, bool need_versions) {
+    for (int i = 0; i < a.nmembers; ++i) {
+        if (a.src[i] == nullptr || a.dst[i] == nullptr || (((uintptr_t)a.src[i] | (uintptr_t)a.dst[i]) & 15) != 0)
+            return false;
+        if (need_versions && (a.ver[i] == nullptr || ((uintptr_t)a.ver[i] & 15) != 0)) return false;
     }
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
+    return true;
+}
+
+// Blocks for `units` at `per_block` each, at most MI355_FUSED_MAX_BLOCKS:
+// what a spin-waiting launch asks of coresident_grid (launch.h).
+uint64_t blocks_wanted(uint64_t units, uint64_t per_block) {
+    const uint64_t grid = (units + per_block - 1) / per_block;
+    return grid < 1 ? 1 : grid > MI355_FUSED_MAX_BLOCKS ? MI355_FUSED_MAX_BLOCKS : grid;
 }
 
 constexpr int kMaxPoke = 1024;
@@ -1018,70 +958,42 @@ extern "C" int mi355_peek_sysload(const unsigned long long *const *src, int n, u
 
 extern "C" int mi355_fused_allreduce(const MI355FusedArgs *a, void *stream) {
     if (a == nullptr || !mi355_op_supported(a->op, a->dtype)) return MI355_E_UNSUP;
-    if (a->nmembers < 2 || a->nmembers > MI355_FUSED_MAX_MEMBERS || a->me < 0 || a->me >= a->nmembers)
-        return MI355_E_INVAL;
+    if (!members_ok(*a, 2)) return MI355_E_INVAL;
     const size_t es = mi355_dtype_size(a->dtype);
     if (a->shard == 0 || (a->shard * es) % 16 != 0) return MI355_E_INVAL;
     // the folds address a member's buffer with 32-bit buffer offsets (ld16_sys_at)
     if (a->n * es >= kMaxFusedBytes || (uint64_t)a->shard * es * (uint64_t)a->nmembers >= kMaxFusedBytes)
         return MI355_E_INVAL;
-    for (int i = 0; i < a->nmembers; ++i)
-        if (a->src[i] == nullptr || a->dst[i] == nullptr || a->sig[i] == nullptr ||
-            (((uintptr_t)a->src[i] | (uintptr_t)a->dst[i]) & 15) != 0 || a->pe[i] < 0 ||
-            a->pe[i] >= MI355_SIG_RSDONE)
-            return MI355_E_INVAL;
+    if (!buffers_ok(*a, a->ordered && !a->oneshot)) return MI355_E_INVAL;
     if (a->oneshot && a->src[a->me] == a->dst[a->me]) return MI355_E_INVAL;  // it overwrites dst while peers read src
-    if (a->ordered && !a->oneshot)
-        for (int i = 0; i < a->nmembers; ++i)
-            if (a->ver[i] == nullptr || ((uintptr_t)a->ver[i] & 15) != 0) return MI355_E_INVAL;
     // enough blocks for the larger of the two legs (one-shot: the whole
     // array), all of them co-resident
     const uint64_t vecs = a->oneshot ? (a->n * es + 15) / 16 : (a->shard * es / 16) * (uint64_t)(a->nmembers - 1);
-    uint64_t grid = (vecs + kBlock - 1) / kBlock;
-    if (grid < 1) grid = 1;
-    if (grid > MI355_FUSED_MAX_BLOCKS) grid = MI355_FUSED_MAX_BLOCKS;
-    hipStream_t st = (hipStream_t)stream;
-    switch (a->dtype) {
-    case MI355_SHORT: return launch_op<int16_t>(*a, (unsigned)grid, st);
-    case MI355_INT: return launch_op<int32_t>(*a, (unsigned)grid, st);
-    case MI355_LONG:
-    case MI355_LONGLONG: return launch_op<int64_t>(*a, (unsigned)grid, st);
-    case MI355_FLOAT: return launch_op<float>(*a, (unsigned)grid, st);
-    case MI355_DOUBLE: return launch_op<double>(*a, (unsigned)grid, st);
-    case MI355_LONGDOUBLE: return launch_op<x80>(*a, (unsigned)grid, st);
-    case MI355_COMPLEXF: return launch_op<cplxf>(*a, (unsigned)grid, st);
-    case MI355_COMPLEXD: return launch_op<cplxd>(*a, (unsigned)grid, st);
-    default: return MI355_E_INVAL;
-    }
+    const uint64_t want = blocks_wanted(vecs, kBlock);
+    return with_op_and_type(a->op, a->dtype, [&](auto o, auto t) {
+        auto k = fused_allreduce<decltype(o)::value, decltype(t)>;
+        return launch_recorded(k, dim3(coresident_grid((const void *)k, want, a->share)), kBlock, (hipStream_t)stream,
+                               *a);
+    });
 }
 
 extern "C" int mi355_fused_pull(const MI355PullArgs *p, void *stream) {
     if (p == nullptr || p->nseg < 0 || p->nseg > MI355_PULL_MAX_SEGS) return MI355_E_INVAL;
     const MI355FusedArgs *a = &p->m;
-    if (a->nmembers < 2 || a->nmembers > MI355_FUSED_MAX_MEMBERS || a->me < 0 || a->me >= a->nmembers)
-        return MI355_E_INVAL;
+    if (!members_ok(*a, 2)) return MI355_E_INVAL;
     uint64_t total = 0;
     for (int k = 0; k < p->nseg; ++k) {
         if (p->nbytes[k] != 0 && (p->dst[k] == nullptr || p->src[k] == nullptr)) return MI355_E_INVAL;
         total += p->nbytes[k];
     }
-    for (int i = 0; i < a->nmembers; ++i)
-        if (a->sig[i] == nullptr || a->pe[i] < 0 || a->pe[i] >= MI355_SIG_RSDONE) return MI355_E_INVAL;
-    uint64_t grid = (total + 16 * kBlock - 1) / (16 * kBlock);
-    if (grid < 1) grid = 1;
-    if (grid > MI355_FUSED_MAX_BLOCKS) grid = MI355_FUSED_MAX_BLOCKS;
-    launch_stamped(fused_pull, coresident_grid((const void *)fused_pull, grid, a->share), kBlock, (hipStream_t)stream,
-                   *p);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
+    const uint64_t want = blocks_wanted(total, 16 * kBlock);
+    return launch_recorded(fused_pull, dim3(coresident_grid((const void *)fused_pull, want, a->share)), kBlock,
+                           (hipStream_t)stream, *p);
 }
 
+// Bare launch: a barrier takes no armed state and records nothing (launch.h).
 extern "C" int mi355_device_barrier(const MI355FusedArgs *a, void *stream) {
-    if (a == nullptr || a->nmembers < 1 || a->nmembers > MI355_FUSED_MAX_MEMBERS || a->me < 0 ||
-        a->me >= a->nmembers)
-        return MI355_E_INVAL;
-    for (int i = 0; i < a->nmembers; ++i)
-        if (a->sig[i] == nullptr || a->pe[i] < 0 || a->pe[i] >= MI355_SIG_RSDONE) return MI355_E_INVAL;
+    if (a == nullptr || !members_ok(*a, 1)) return MI355_E_INVAL;
     hipLaunchKernelGGL(device_barrier, dim3(1), dim3(64), 0, (hipStream_t)stream, *a);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : (int)e;
@@ -1091,35 +1003,22 @@ extern "C" int mi355_fused_server(const MI355FusedArgs *a, MI355ServerMailbox *m
                                   unsigned long long idle_ticks, unsigned long long grid_vecs, void *stream) {
     if (a == nullptr || mbox == nullptr || !mi355_op_supported(a->op, a->dtype)) return MI355_E_UNSUP;
     // one member: the 1-PE identity (one-shot copy of the caller's source)
-    if (a->nmembers < 1 || a->nmembers > MI355_FUSED_MAX_MEMBERS || a->me < 0 || a->me >= a->nmembers)
-        return MI355_E_INVAL;
+    if (!members_ok(*a, 1)) return MI355_E_INVAL;
     if (a->host_src != nullptr || a->host_dst != nullptr || a->host_flag == nullptr) return MI355_E_INVAL;
     if (grid_vecs * 16 >= kMaxFusedBytes) return MI355_E_INVAL;   // 32-bit buffer offsets (ld16_sys_at)
-    for (int i = 0; i < a->nmembers; ++i)
-        if (a->src[i] == nullptr || a->dst[i] == nullptr || a->sig[i] == nullptr ||
-            (((uintptr_t)a->src[i] | (uintptr_t)a->dst[i]) & 15) != 0 || a->pe[i] < 0 ||
-            a->pe[i] >= MI355_SIG_RSDONE)
-            return MI355_E_INVAL;
-    if (a->ordered)
-        for (int i = 0; i < a->nmembers; ++i)
-            if (a->ver[i] == nullptr || ((uintptr_t)a->ver[i] & 15) != 0) return MI355_E_INVAL;
+    if (!buffers_ok(*a, a->ordered != 0)) return MI355_E_INVAL;
     // the grid a launched call moving grid_vecs 16-byte vectors per PE gets
-    uint64_t grid = (grid_vecs + kBlock - 1) / kBlock;
-    if (grid < 1) grid = 1;
-    if (grid > MI355_FUSED_MAX_BLOCKS) grid = MI355_FUSED_MAX_BLOCKS;
-    hipStream_t st = (hipStream_t)stream;
-    switch (a->dtype) {
-    case MI355_SHORT: return launch_server<int16_t>(*a, mbox, first_seq, idle_ticks, (unsigned)grid, st);
-    case MI355_INT: return launch_server<int32_t>(*a, mbox, first_seq, idle_ticks, (unsigned)grid, st);
-    case MI355_LONG:
-    case MI355_LONGLONG: return launch_server<int64_t>(*a, mbox, first_seq, idle_ticks, (unsigned)grid, st);
-    case MI355_FLOAT: return launch_server<float>(*a, mbox, first_seq, idle_ticks, (unsigned)grid, st);
-    case MI355_DOUBLE: return launch_server<double>(*a, mbox, first_seq, idle_ticks, (unsigned)grid, st);
-    case MI355_LONGDOUBLE: return launch_server<x80>(*a, mbox, first_seq, idle_ticks, (unsigned)grid, st);
-    case MI355_COMPLEXF: return launch_server<cplxf>(*a, mbox, first_seq, idle_ticks, (unsigned)grid, st);
-    case MI355_COMPLEXD: return launch_server<cplxd>(*a, mbox, first_seq, idle_ticks, (unsigned)grid, st);
-    default: return MI355_E_INVAL;
-    }
+    const uint64_t want = blocks_wanted(grid_vecs, kBlock);
+    return with_op_and_type(a->op, a->dtype, [&](auto o, auto t) {
+        auto k = fused_server<decltype(o)::value, decltype(t)>;
+        // recorded, but an armed event pair stays armed (launch.h): the
+        // resident grid outlives the call that starts it
+        const dim3 grid(coresident_grid((const void *)k, want, a->share));
+        t_launch.record((const void *)k, grid);
+        hipLaunchKernelGGL(k, grid, dim3(kBlock), 0, (hipStream_t)stream, *a, mbox, first_seq, idle_ticks);
+        hipError_t e = hipGetLastError();
+        return e == hipSuccess ? 0 : (int)e;
+    });
 }
 
 #ifdef MI355_FUSED_PHASES

@@ -2,10 +2,14 @@
 // reads the pointers' phases. Host-only integer arithmetic on addresses (no
 // HIP: tests/native/launch_plan_check.cpp compiles it with plain g++ and
 // enumerates every phase combination); combine_kernels.h's launchers turn the
-// plan into a kernel and a grid.
+// plan into a kernel and a grid. Below the plan, the two grid caps of the
+// launch layer (launch.h hands them the device's CU count and the occupancy
+// query's answer), the same way: arithmetic only.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
+
+#include "residency.h"
 
 namespace mi355k {
 
@@ -80,6 +84,30 @@ inline LaunchPlan plan_launch(size_t es, bool shiftable, const void *const *outs
         kind = PLAN_SHIFT;
     }
     return {kind, head, (n - head) / V, (n - head) % V};
+}
+
+// The streaming cap (launch.h, grid_for): blocks that cover `units` once at
+// `per_pass` units per block, at least one, at most blocks_per_cu per CU --
+// the kernels' grid-stride loops cover the rest.
+inline unsigned streaming_grid(uint64_t units, uint64_t per_pass, int cus, int blocks_per_cu) {
+    uint64_t want = (units + per_pass - 1) / per_pass;
+    const uint64_t cap = (uint64_t)cus * blocks_per_cu;
+    if (want < 1) want = 1;
+    return (unsigned)(want < cap ? want : cap);
+}
+
+// The co-residency cap (launch.h, coresident_grid): `want` blocks, at most
+// what `share` processes on one GPU can each keep resident at once. Per CU:
+// `occupancy` (the occupancy query's blocks per CU at 256 threads; a failed
+// query counts as 1), at most MI355_FUSED_RESIDENT_PER_CU, one fewer as a
+// margin but never none.
+inline unsigned coresident_cap(int occupancy, int cus, int share, uint64_t want) {
+    int n = occupancy < MI355_FUSED_RESIDENT_PER_CU ? occupancy : MI355_FUSED_RESIDENT_PER_CU;
+    const int per_cu = n > 1 ? n - 1 : 1;
+    uint64_t cap = (uint64_t)per_cu * (uint64_t)cus / (uint64_t)(share > 1 ? share : 1);
+    if (cap < 1) cap = 1;
+    if (want > cap) want = cap;
+    return (unsigned)(want < 1 ? 1 : want);
 }
 
 }  // namespace mi355k

@@ -2,7 +2,8 @@
 //
 // Every block of a fused_allreduce / fused_server / fused_pull grid waits for
 // the grid's last block and for the other members, so all of them must be
-// resident at once (fused.hip, coresident_grid). A launch takes at most
+// resident at once (launch.h, coresident_grid; the arithmetic: launch_plan.h,
+// coresident_cap). A launch takes at most
 // min(occupancy API, MI355_FUSED_RESIDENT_PER_CU) - 1 blocks per CU. The API
 // ignores the SGPR admission limit of 256-thread blocks,
 // floor(800 / (ceil(sgpr / 16) * 16 + 16)) per CU (MI355X_MICROARCH.md

@@ -603,6 +603,13 @@ class Shmem:
         self.lib.mi355_last_launch_grid(ctypes.byref(gx), ctypes.byref(gy))
         return gx.value, gy.value
 
+    def last_kernel_name(self):
+        """demangled name of that same kernel (mi355_last_kernel, mi355_kernel_name); "" before the first launch"""
+        self.lib.mi355_last_kernel.restype = ctypes.c_void_p
+        self.lib.mi355_kernel_name.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t]
+        buf = ctypes.create_string_buffer(512)
+        return buf.value.decode() if self.lib.mi355_kernel_name(self.lib.mi355_last_kernel(), buf, 512) == 0 else ""
+
     def last_call_info(self):
         """dict of shmemx_last_call_info, or None before the first call"""
         ci = CallInfo()

@@ -8,7 +8,8 @@ A case: {"id", "kind": alltoall | alltoalls | fcollect | sum, "bits", "n",
 "dst", "sst", "sets", "target": device | host | pageable | mixed, "source":
 device | host, "seed", "slen", "tlen"}; slen / tlen are the elements of the
 source filled and of the target read back (sentinel -7 first). "report_grid":
-also save mi355_last_launch_grid after the call, as "grid<id>".
+also save mi355_last_launch_grid after the call, as "grid<id>", and that
+kernel's name, as "kernel<id>".
 """
 import ctypes
 import json
@@ -82,6 +83,7 @@ def run_case(shm, c, me, bufs, results):
     if c.get("report_grid"):
         # the grid of the strided kernel this PE just launched (the test's pass rule)
         results[f"grid{c['id']}"] = np.array(shm.last_launch_grid())
+        results[f"kernel{c['id']}"] = np.array([shm.last_kernel_name()])
     if kt == "device":
         got = shm.get(tgt, tlen, dt)
     else:

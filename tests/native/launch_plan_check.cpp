@@ -7,6 +7,10 @@
 //   launch_plan_check plan CASE...     one line "KIND head nvec tail" per case,
 //                                      CASE = es:shiftable:n:out,out,..:src,src,..
 //                                      (byte addresses; "-" for no outputs)
+//   launch_plan_check caps CAP...      the grid of each, one per line: CAP =
+//                                      stream:units:per_pass:cus:blocks_per_cu (streaming_grid) or
+//                                      resident:occupancy:cus:share:want (coresident_cap)
+//   launch_plan_check capsweep         the two caps' sweep: "<cases> cases, digest <hex>, <n> violations"
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -152,7 +156,78 @@ static std::vector<uintptr_t> parse_list(const std::string &s) {
     return v;
 }
 
+// The two grid caps over every combination of the values below: 1 <= grid <=
+// max(cap, 1) with the cap worked out here from the rule, never fewer blocks
+// for more work, and a digest of every grid.
+static int cap_sweep() {
+    long cases = 0, bad = 0;
+    auto require = [&](bool ok, const char *what, uint64_t a, uint64_t b, uint64_t c, uint64_t d, unsigned grid) {
+        if (!ok && ++bad <= 20)
+            printf("VIOLATION %s: %llu %llu %llu %llu -> %u\n", what, (unsigned long long)a, (unsigned long long)b,
+                   (unsigned long long)c, (unsigned long long)d, grid);
+    };
+    const int cus_of[] = {1, 4, 256, 304};
+    for (uint64_t per_pass : {1ull, 256ull, 1024ull, 4096ull})
+        for (int cus : cus_of)
+            for (int bpc : {1, 2, 4, 8, 1 << 20}) {
+                const uint64_t cap = (uint64_t)cus * bpc, full = cap * per_pass;
+                const uint64_t units[] = {0, 1, per_pass - 1, per_pass, per_pass + 1, full - 1, full, full + 1,
+                                          1ull << 31, 1ull << 40, 1ull << 62};
+                for (uint64_t u : units) {   // not sorted: monotonicity is checked against every smaller one
+                    const unsigned g = mi355k::streaming_grid(u, per_pass, cus, bpc);
+                    ++cases;
+                    digest_u64(g, 4);
+                    require(g >= 1 && g <= cap, "streaming range", u, per_pass, cus, bpc, g);
+                    const uint64_t cover = (u + per_pass - 1) / per_pass;
+                    require(g == (cover < 1 ? 1 : cover < cap ? cover : cap), "streaming rule", u, per_pass, cus, bpc, g);
+                    for (uint64_t v : units)
+                        if (v <= u)
+                            require(mi355k::streaming_grid(v, per_pass, cus, bpc) <= g, "streaming monotone", u, v, cus,
+                                    bpc, g);
+                }
+            }
+    for (int occ = 0; occ <= 10; ++occ)
+        for (int cus : cus_of)
+            for (int share : {-1, 0, 1, 2, 3, 8, 9, 16, 64}) {
+                const int n = occ < MI355_FUSED_RESIDENT_PER_CU ? occ : MI355_FUSED_RESIDENT_PER_CU;
+                const uint64_t per_cu = n - 1 > 1 ? n - 1 : 1;
+                uint64_t cap = per_cu * (uint64_t)cus / (uint64_t)(share > 1 ? share : 1);
+                if (cap < 1) cap = 1;
+                const uint64_t wants[] = {0, 1, 2, 5, 255, 256, 257, cap - 1, cap, cap + 1, 1000000, 1ull << 40};
+                for (uint64_t w : wants) {
+                    const unsigned g = mi355k::coresident_cap(occ, cus, share, w);
+                    ++cases;
+                    digest_u64(g, 4);
+                    require(g >= 1 && g <= cap, "co-residency range", occ, cus, (uint64_t)(int64_t)share, w, g);
+                    require(g == (w < 1 ? 1 : w < cap ? w : cap), "co-residency rule", occ, cus, (uint64_t)(int64_t)share,
+                            w, g);
+                    for (uint64_t v : wants)
+                        if (v <= w)
+                            require(mi355k::coresident_cap(occ, cus, share, v) <= g, "co-residency monotone", occ, cus,
+                                    w, v, g);
+                }
+            }
+    printf("%ld cases, digest %016llx, %ld violations\n", cases, (unsigned long long)g_digest, bad);
+    return bad == 0 ? 0 : 1;
+}
+
 int main(int argc, char **argv) {
+    if (argc > 1 && strcmp(argv[1], "capsweep") == 0) return cap_sweep();
+    if (argc > 1 && strcmp(argv[1], "caps") == 0) {
+        // stream:UNITS:PER_PASS:CUS:BLOCKS_PER_CU | resident:OCCUPANCY:CUS:SHARE:WANT -> the grid
+        for (int i = 2; i < argc; ++i) {
+            char kind[16];
+            long long v[4];
+            if (sscanf(argv[i], "%15[a-z]:%lld:%lld:%lld:%lld", kind, &v[0], &v[1], &v[2], &v[3]) != 5) return 2;
+            if (strcmp(kind, "stream") == 0)
+                printf("%u\n", mi355k::streaming_grid((uint64_t)v[0], (uint64_t)v[1], (int)v[2], (int)v[3]));
+            else if (strcmp(kind, "resident") == 0)
+                printf("%u\n", mi355k::coresident_cap((int)v[0], (int)v[1], (int)v[2], (uint64_t)v[3]));
+            else
+                return 2;
+        }
+        return 0;
+    }
     if (argc > 1 && strcmp(argv[1], "plan") == 0) {
         for (int i = 2; i < argc; ++i) {
             std::vector<std::string> f;

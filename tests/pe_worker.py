@@ -23,6 +23,18 @@ def members(start, logstride, size):
     return [start + i * (1 << logstride) for i in range(size)]
 
 
+def report_launch(shm, c, results):
+    """"report_launch": right after the case's call, save the kernel layer's
+    record of this PE's last launch -- its kernel's name and its grid -- and
+    what the runtime reports of the call (schedule, bytes per buffer)"""
+    if not c.get("report_launch"):
+        return
+    results[f"{c['id']}_kernel"] = np.array([shm.last_kernel_name()])
+    results[f"{c['id']}_grid"] = np.array(shm.last_launch_grid())
+    info = shm.last_call_info() or {"schedule": "", "bytes_per_buffer": 0}
+    results[f"{c['id']}_call"] = np.array([info["schedule"], str(info["bytes_per_buffer"])])
+
+
 def dm_source(c, pe):
     """Source block of PE pe for a data-movement case (collect: length varies by PE)."""
     import _inputs
@@ -75,6 +87,7 @@ def run_datamove(shm, c, me, da, db, ha, hb, results):
         f = getattr(L, f"shmem_broadcast{bits}")
         f.argtypes = [vp, vp, sz, i, i, i, i, vp]
         f(tgt, sa, c["n"], c["root"], start, logstride, size, psync)
+        report_launch(shm, c, results)
     elif kind in ("fcollect", "collect"):
         f = getattr(L, f"shmem_{kind}{bits}")
         f.argtypes = [vp, vp, sz, i, i, i, vp]
@@ -500,6 +513,7 @@ def main():
             fortran_to_all(shm, op, dtype, dst, src, n, *mine)
         else:
             shm.to_all(op, dtype, dst, src, n, *mine)
+        report_launch(shm, c, results)
         if busy_t0 is not None:
             import time
             results[str(c["id"]) + "_seconds"] = np.array([time.perf_counter() - busy_t0])

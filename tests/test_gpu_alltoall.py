@@ -222,6 +222,25 @@ def test_alltoall_four_pes(tmp_path, fused, kernel_results):
 
 
 @pytest.mark.multipe
+def test_closing_device_barrier_leaves_the_strided_launch_on_record(tmp_path):
+    """The device barrier launches bare: it records nothing. After a strided
+    alltoalls32 on 2 PEs -- device barrier, strided kernel, device barrier --
+    the kernel layer's last launch is still the strided kernel, name and grid:
+    5,000 elements per block at 1,024 per kernel block are 5 blocks in x (far
+    below the cap of 8 per CU), one row per member in y. (Had the barrier
+    recorded itself, the all-to-all tests' pass rule above would read 1 x 1.)"""
+    c = case(0, "alltoalls", 32, 5000, [[0, 0, 2]], 2, 3, report_grid=True)
+    res = run_a2a(2, [c], tmp_path)
+    check(res, [c])
+    for pe in range(2):
+        kernel, grid = str(res[pe]["kernel0"][0]), tuple(int(v) for v in res[pe]["grid0"])
+        print(f"barrier-record | alltoalls32 (2,3) PE {pe} | {kernel[:70]} | {grid}")
+        assert "strided_pull" in kernel and "device_barrier" not in kernel, (pe, kernel)
+        assert grid == (5, 2), (pe, grid)
+    cached_source.cache_clear()
+
+
+@pytest.mark.multipe
 def test_alltoall_four_pes_off_alignment(tmp_path):
     """Source and target 4 bytes into their allocations: the vector sides
     peel a head, the copy kernel takes its co-aligned path."""

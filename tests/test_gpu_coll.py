@@ -6,7 +6,7 @@ import pytest
 
 import oracle
 from pe_worker import dm_source
-from test_gpu_multipe import members, run_pes
+from test_gpu_multipe import check, make_cases, members, run_pes
 
 pytestmark = [pytest.mark.gpu, pytest.mark.multipe]
 
@@ -103,6 +103,40 @@ def test_collectives_four_pes(tmp_path, fused):
             cases.append(case(cid, "putget", bits, 51, [[0, 0, 4]], put_from=pf)); cid += 1
     results = run_pes(4, cases, tmp_path, extra_env=None if fused == "fused" else {"SHMEM_FUSED_MAX_BYTES": "0"})
     check_dm(results, cases)
+
+
+def test_fused_launches_record_their_kernel_and_grid(tmp_path):
+    """The kernel layer's record of a thread's last launch (mi355_last_kernel,
+    mi355_last_launch_grid) after the two one-launch collectives, on 2 PEs
+    under the default thresholds: the name and the grid describe the same
+    launch. A blocking double sum of 1,024 elements is the one-shot fused
+    schedule: ceil(n * 8 / 16) = 512 vectors at 256 per block, 2 blocks, far
+    below the co-residency cap of 5 x CUs / 2; 1,023 elements (8,184 bytes,
+    still 512 vectors) by the same formula from the bytes the call reports.
+    shmem_broadcast64 of 512 elements is the fused pull: 4,096 bytes are one
+    block's 4,096-byte pass (the root pulls nothing: one block as well)."""
+    reduce_cases = make_cases([("sum", "double")], 1024, [[0, 0, 2]], "dev", "auto", 0) + \
+        make_cases([("sum", "double")], 1023, [[0, 0, 2]], "dev", "auto", 1)
+    bcast = case(2, "broadcast", 64, 512, [[0, 0, 2]], root=1)
+    cases = reduce_cases + [bcast]
+    for c in cases:
+        c["report_launch"] = True
+    results = run_pes(2, cases, tmp_path)
+    check(results, reduce_cases)
+    check_dm(results, [bcast])
+    for pe in range(2):
+        for c in reduce_cases:
+            schedule, nbytes = results[pe][f"{c['id']}_call"]
+            kernel, grid = str(results[pe][f"{c['id']}_kernel"][0]), tuple(int(v) for v in results[pe][f"{c['id']}_grid"])
+            print(f"fused-record | double sum n {c['n']} PE {pe} | {schedule} {nbytes} B | {kernel[:60]} | {grid}")
+            # 8,184 bytes are within the one-shot threshold too (sched_plan.h oneshot_fits: no padding involved)
+            assert schedule == "fused-oneshot" and int(nbytes) == c["n"] * 8, (pe, c["n"], schedule, nbytes)
+            assert "fused_allreduce" in kernel, (pe, c["n"], kernel)
+            vectors = (int(nbytes) + 15) // 16
+            assert vectors == 512 and grid == ((vectors + 255) // 256, 1) == (2, 1), (pe, c["n"], grid)
+        kernel, grid = str(results[pe]["2_kernel"][0]), tuple(int(v) for v in results[pe]["2_grid"])
+        print(f"fused-record | broadcast64 n 512 PE {pe} | {kernel[:60]} | {grid}")
+        assert "fused_pull" in kernel and grid == (1, 1), (pe, kernel, grid)
 
 
 def test_collectives_eight_pes(tmp_path):

@@ -4,7 +4,8 @@ head peeled to the outputs' 128-byte line) compiled for the host under
 AddressSanitizer and UBSan and run as an ordinary program
 (tests/native/launch_plan_check.cpp): its invariants over every phase
 combination of outputs and sources, a digest of all the plans, and a dozen
-cases spelt out. The GPU side of the same decisions is
+cases spelt out; and the launch layer's two grid caps (the streaming cap and
+the spin-waiting grids' co-residency cap) the same way. The GPU side of the same decisions is
 test_gpu_combine.py::test_launch_identity_matches_recorded_table."""
 import os
 import subprocess
@@ -78,6 +79,55 @@ NAMED = [
     ("no outputs, one source off: nothing to align to",
      4, 1, 1000, [], [S[0], S[1] + 4], "ELEMENTS 0 1000 0"),
 ]
+
+
+# The two grid caps of the launch layer (launch_plan.h streaming_grid and
+# coresident_cap). FNV-1a over every grid of the sweep, recorded from the two
+# function bodies these replaced -- grid_for of combine_kernels.h and
+# coresident_grid of fused.hip, their device queries turned into arguments --
+# run through this same enumeration before they were deleted; the new
+# functions gave the same grid on every case.
+CAP_CASES = 5632
+CAP_DIGEST = "8d705bf8d63b622b"
+
+# ceil(units / per_pass), at least 1, at most cus x blocks_per_cu
+STREAMING = [  # (units, per_pass, cus, blocks_per_cu) -> grid
+    ((0, 1024, 256, 8), 1),
+    ((1024, 1024, 256, 8), 1),
+    ((1025, 1024, 256, 8), 2),
+    ((2**40, 1024, 256, 1), 256),
+    ((2**40, 1024, 304, 2), 608),
+]
+# per_cu = max(min(occupancy, 6) - 1, 1); cap = max(per_cu x cus / max(share, 1), 1); max(min(want, cap), 1)
+RESIDENT = [  # (occupancy, cus, share, want) -> grid
+    ((8, 256, 1, 10**6), 1280),
+    ((8, 256, 9, 10**6), 142),      # 1280 / 9
+    ((3, 256, 2, 10**6), 256),      # 2 x 256 / 2
+    ((1, 256, 1, 10**6), 256),      # the margin never reaches zero
+    ((0, 256, 1, 10**6), 256),      # a failed query counts as one
+    ((6, 4, 64, 10**6), 1),
+    ((8, 256, 0, 5), 5),            # share 0 treated as 1
+    ((8, 256, 1, 0), 1),
+]
+
+
+def test_grid_caps_named_cases(exe):
+    cases = [("stream", a, want) for a, want in STREAMING] + [("resident", a, want) for a, want in RESIDENT]
+    out = subprocess.run([exe, "caps"] + [":".join([kind] + [str(v) for v in a]) for kind, a, _ in cases],
+                         capture_output=True, text=True, timeout=60)
+    assert out.returncode == 0, out.stdout + out.stderr
+    got = out.stdout.split()
+    assert len(got) == len(cases), out.stdout
+    for (kind, a, want), g in zip(cases, got):
+        assert int(g) == want, (kind, a)
+
+
+def test_grid_caps_sweep_keeps_the_invariants_and_the_recorded_grids(exe):
+    out = subprocess.run([exe, "capsweep"], capture_output=True, text=True, timeout=60)
+    assert out.returncode == 0, out.stdout + out.stderr
+    assert f"{CAP_CASES} cases" in out.stdout, out.stdout
+    assert "0 violations" in out.stdout, out.stdout
+    assert f"digest {CAP_DIGEST}," in out.stdout, out.stdout
 
 
 def test_named_cases(exe):

@@ -4,7 +4,7 @@
 Every block of a fused_allreduce / fused_server / fused_pull grid waits for
 the others (fused.hip), so a launch is capped at
 min(occupancy API, MI355_FUSED_RESIDENT_PER_CU) - 1 blocks per CU
-(coresident_grid, csrc/residency.h). The occupancy API ignores the SGPR
+(csrc/launch.h coresident_grid, csrc/residency.h). The occupancy API ignores the SGPR
 admission limit of 256-thread blocks, floor(800 / (ceil(sgpr/16)*16 + 16))
 per CU (MI355X_MICROARCH.md "Residency"); a kernel that grows past it would
 make the cap too high, and the symptom is a hang, not an error. This reads
