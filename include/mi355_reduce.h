@@ -180,7 +180,11 @@ int mi355_amo (int op, int width, void *target, unsigned long long value, unsign
  * MI355_LONG, MI355_LONGLONG (wrapping), MI355_FLOAT, MI355_DOUBLE. Both
  * pointers element-aligned, nothing more; the source is only read. Several
  * callers may add into one target at once; a float or double sum then
- * depends on the arrival order in its last bits. */
+ * depends on the arrival order in its last bits. Each float or double add is
+ * one correctly rounded IEEE add: nearest-even, gradual underflow (no
+ * subnormal operand or result is flushed), overflow to Inf, IEEE zero signs.
+ * Where an add's result is a NaN (a NaN operand, Inf + -Inf) the element holds
+ * a NaN and nothing more is specified: not its sign, payload or quiet bit. */
 int mi355_atomic_add_v (int dtype, void *target, const void *source, size_t n, void *stream);
 
 /* The grid mi355_atomic_add_v launches for n elements on a GPU of `cus`

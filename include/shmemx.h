@@ -806,7 +806,13 @@ void shmemx_bfloat16_min_exscan (shmemx_bfloat16_t *target, shmemx_bfloat16_t *s
  *      in the host heap (a host loop of atomic adds; for float and double a
  *      compare-and-swap on the bit pattern). Integers wrap. A float or double
  *      sum depends on the arrival order in its last bits when several PEs add
- *      at once. Blocking: complete at the target on return. Not collective. ---- */
+ *      at once. Each float or double add is one correctly rounded IEEE add
+ *      (nearest-even, gradual underflow, overflow to Inf, IEEE zero signs),
+ *      the same bits in either heap. Where an add's result is a NaN (a NaN
+ *      operand, Inf + -Inf) the element holds a NaN and nothing more is
+ *      specified: its sign, payload and quiet bit may differ between the
+ *      heaps and between builds (the host compiler may commute the operands).
+ *      Blocking: complete at the target on return. Not collective. ---- */
 void shmemx_int_atomic_add_v (int *target, const int *source, size_t nelems, int pe);
 void shmemx_long_atomic_add_v (long *target, const long *source, size_t nelems, int pe);
 void shmemx_longlong_atomic_add_v (long long *target, const long long *source, size_t nelems, int pe);

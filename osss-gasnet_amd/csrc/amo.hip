@@ -40,8 +40,16 @@
 // compare-and-swap loop (this translation unit alone is built with
 // -munsafe-fp-atomics: the heaps are ordinary device memory, hipMalloc'd,
 // where the hardware instruction is valid; the Makefile's rule says the
-// same). A hardware float add flushes no denormals on gfx950 and rounds to
-// nearest even, like the CAS loop's v_add would.
+// same). The memory-side add is one correctly rounded IEEE add, as the CAS
+// loop's v_add would be and as the host heap's SSE add is: nearest-even with
+// ties to the even neighbour, subnormal operands and results kept (MODE.denorm
+// does not reach it, and nothing is flushed), max + half an ulp to Inf,
+// -0 + -0 = -0 and x + (-x) = +0. Measured, not assumed:
+// tests/test_gpu_atomic.py::test_accumulate_kernel_float_semantics runs the
+// operand table of tests/_fp_add_cases.py through atomic_add_v<float> and
+// <double> and compares every non-NaN row with an exact model in every bit.
+// Where the result is a NaN, that it is a NaN is all that is promised: which
+// sign, payload and quiet bit the atomic unit returns is not specified.
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>

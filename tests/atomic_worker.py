@@ -22,11 +22,13 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(os.path.dirname(HERE), "osss-gasnet_amd"))
 spec = json.load(open(sys.argv[1]))
-if "accumulate" in spec["tests"]:
+if "accumulate" in spec["tests"] or ("accumulate_fp" in spec["tests"] and spec["heap"] == "device"):
     # torch brings a HIP runtime of its own: it has to be loaded before the
     # library, as in the other torch workers, so that one runtime serves both
     import torch  # noqa: E402,F401
 import shmem_reduce  # noqa: E402
+
+import _fp_add_cases as fp  # noqa: E402  (tests/, this script's directory)
 
 shm = shmem_reduce.Shmem()
 shm.init()
@@ -330,7 +332,11 @@ def acc_source(name, base, pe):
 def test_accumulate(heap):
     """every PE adds its own array into the last PE's, concurrently, between two
     barriers; n = one grid pass + 1; sources in device memory, in pageable
-    host memory, and a torch tensor through the tensor form"""
+    host memory, and a torch tensor through the tensor form. Float and double
+    sums of these small integers are exact: what the add does when it rounds,
+    underflows, overflows or meets a zero, an Inf or a NaN is
+    test_accumulate_fp's, and rounded sums under contention
+    test_accumulate_orders'."""
     _, pass_elems = shm.atomic_add_v_plan(1 << 40, shm.device_cus())
     n = pass_elems + 1
     r = npes - 1
@@ -379,6 +385,108 @@ def test_accumulate(heap):
             if dsrc is not None:
                 shm.free_device(dsrc)
             shm.free_device(target)
+
+
+FP_GUARD = 64       # sentinel elements on both sides of the table's target: a multiple of 16 bytes
+FP_SENT = -12345.0
+
+
+def _bits(a):
+    return np.ascontiguousarray(a).view(np.uint8)
+
+
+def test_accumulate_fp(heap):
+    """PE 0 alone adds the operand table of tests/_fp_add_cases.py into PE 1's
+    target, one element off a 16-byte boundary between sentinels: a single
+    adder, so every non-NaN row has one right answer in every bit and every
+    NaN row is a NaN. Device heap: a device source, a pageable host source
+    (staged through scratch C) and a torch tensor. Host heap: a pageable
+    source and one in the host heap, neither needing a device."""
+    assert npes == 2
+    for name in ("float", "double"):
+        t, s = fp.cases(name)
+        dt, n = t.dtype, t.size
+        es = dt.itemsize
+        lo, hi = FP_GUARD + 1, FP_GUARD + 1 + n
+        for kind in (("device", "host", "torch") if heap == "device" else ("host", "heap")):
+            buf = np.full(hi + FP_GUARD, FP_SENT, dt)
+            _bits(buf[lo:hi])[:] = _bits(t)                      # bytes: no NaN passes through a float move
+            if kind == "torch":
+                tt = shm.heap_tensor(buf.size, getattr(torch, dt.name))
+                base = tt.data_ptr()
+            else:
+                base = alloc(heap, buf.nbytes)
+            assert base % 16 == 0
+            poke(heap, base, buf)
+            mine = s.copy()
+            src = None
+            if kind in ("device", "heap"):
+                src = alloc(kind.replace("heap", "host"), n * es)
+                poke(kind.replace("heap", "host"), src, mine)
+            elif kind == "torch":
+                src_t = torch.from_numpy(mine.copy()).cuda()
+            shm.barrier_all()
+            if me == 0:
+                if kind == "torch":
+                    shm.atomic_add_v_tensors(tt[lo:hi], src_t, 1)
+                else:
+                    shm.atomic_add_v(name, base + lo * es, src if src is not None else mine.ctypes.data, n, 1)
+            shm.barrier_all()
+            got = peek(heap, base, buf.size, dt)
+            where = f"{heap} heap, {kind} source, PE {me}"
+            assert (_bits(got[:lo]) == _bits(buf[:lo])).all() and (_bits(got[hi:]) == _bits(buf[hi:])).all(), \
+                (name, where, "sentinels changed")
+            if me == 1:
+                msg = fp.mismatches(name, got[lo:hi], where=where)
+                assert msg is None, msg
+            else:
+                assert (_bits(got) == _bits(buf)).all(), (name, where, "the adder's own copy changed")
+            after = {"device": lambda: shm.get(src, n, dt), "heap": lambda: peek("host", src, n, dt),
+                     "host": lambda: mine, "torch": lambda: src_t.cpu().numpy()}[kind]()
+            assert (_bits(after) == _bits(s)).all(), (name, where, "source changed")
+            shm.barrier_all()
+            if src is not None:
+                free(kind.replace("heap", "host"), src)
+            free(heap, base)
+
+
+def test_accumulate_orders(heap):
+    """every PE adds its own full-mantissa array (magnitudes in [1, 256),
+    random signs) into the last PE's target at once, between two barriers;
+    n = 4,096 + 64. Every element must equal the sum in one of the npes!
+    arrival orders, each rounded in the format on top of the initial value
+    (tests/_fp_add_cases.py orders_case: no term can be absorbed, so a lost
+    or doubled update equals none of them). Not vacuous: at least 25 % of
+    the elements (2 PEs; the inputs give 27.7 %) or 75 % (4 PEs; 82.5 %)
+    have two or more distinct legal results."""
+    r = npes - 1
+    for name in ("float", "double"):
+        init, sources, legal, share = fp.orders_case(name, npes)
+        assert share >= fp.ORDERS_MIN_SHARE[npes], (name, npes, share)
+        dt, n = init.dtype, init.size
+        target = alloc(heap, n * dt.itemsize)
+        poke(heap, target, init)
+        src = None
+        if heap == "device":
+            src = alloc("device", n * dt.itemsize)
+            poke("device", src, sources[me])
+        mine = sources[me].copy()
+        shm.barrier_all()
+        shm.atomic_add_v(name, target, src if src is not None else mine.ctypes.data, n, r)
+        shm.barrier_all()
+        got = peek(heap, target, n, dt)
+        if me == r:
+            bad = fp.illegal_elements(name, npes, got)
+            u = legal.dtype
+            assert bad.size == 0, (name, heap, f"{bad.size} of {n} elements equal the sum in no arrival order", bad[:4],
+                                   [hex(v) for v in got.view(u)[bad[:4]]],
+                                   [[hex(v) for v in legal[:, i]] for i in bad[:2]])
+        else:
+            assert (_bits(got) == _bits(init)).all(), (name, heap, "a target that nobody added into changed")
+        shm.barrier_all()
+        if src is not None:
+            free("device", src)
+        free(heap, target)
 
 
 checked, failures = [], []

@@ -242,7 +242,10 @@ def test_misaligned_target_aborts_by_name(tmp_path):
 def test_accumulate_on_the_host_heap(tmp_path):
     """shmemx_<T>_atomic_add_v with a host-heap target: 3 PEs add into PE 2's
     array at once; integers wrap, float and double sums of small integers
-    are exact in any order"""
+    are exact in any order. The arithmetic of the float and double add
+    (rounding, underflow, overflow, zeros, Inf, NaN) is
+    tests/test_fp_add_cases.py's and test_accumulate_float_semantics', rounded
+    sums under contention test_accumulate_arrival_orders'."""
     body = """
     import numpy as np
     n = 3001
@@ -272,3 +275,19 @@ def test_accumulate_on_the_host_heap(tmp_path):
     """
     for rc, out in test_bootstrap.spawn(3, body, tmp_path):
         assert rc == 0 and "ok" in out, out
+
+
+def test_accumulate_float_semantics(tmp_path):
+    """worker test accumulate_fp on the host heap: PE 0 alone adds the operand
+    table of tests/_fp_add_cases.py into PE 1's target, from a pageable source
+    and from one in the host heap; every non-NaN row against the exact model
+    in every bit"""
+    run_workers(2, "host", ["accumulate_fp"], tmp_path)
+
+
+@pytest.mark.parametrize("npes", [2, 4])
+def test_accumulate_arrival_orders(tmp_path, npes):
+    """worker test accumulate_orders on the host heap: full-mantissa arrays
+    from every PE at once; every element is the rounded sum in one of the
+    npes! arrival orders"""
+    run_workers(npes, "host", ["accumulate_orders"], tmp_path)

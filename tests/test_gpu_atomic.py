@@ -13,7 +13,12 @@ Expected values: Python integers reduced modulo 2^32 / 2^64 for the single
 operations; numpy for the accumulate -- wrapping integer sums, and for float
 and double sources drawn from small integers (|x| <= 512 on top of |t| <= 64:
 every partial sum is an integer below 2^12, exact in either format), so the
-comparison is of bits, with no tolerance.
+comparison is of bits, with no tolerance. The arithmetic of the float and
+double add itself -- one global_atomic_add_f32 / _f64 per element in the
+memory-side atomic unit -- is held to the exact model of
+tests/_fp_add_cases.py on its operand table (ties, sticky bits, gradual
+underflow, overflow, zeros, Inf, NaN): the kernel alone, the library paths
+with one adder, and every arrival order's rounded sum with several.
 """
 import ctypes
 import os
@@ -23,6 +28,7 @@ import sys
 import numpy as np
 import pytest
 
+import _fp_add_cases as fp
 import test_bootstrap
 from test_atomic_cpu import HERE, ROOT, SEMANTIC, build_c, run_workers
 
@@ -50,6 +56,24 @@ def test_device_heap_wait_until(tmp_path):
 @pytest.mark.parametrize("npes", [2, 4, 8])
 def test_accumulate_across_pes(tmp_path, npes):
     run_workers(npes, "device", ["accumulate"], tmp_path, gpu=True, timeout=300)
+
+
+@pytest.mark.multipe
+def test_accumulate_float_semantics_across_pes(tmp_path):
+    """worker test accumulate_fp on the device heap: PE 0 alone adds the
+    operand table into PE 1's target from a device source, a pageable host
+    source and a torch tensor; every non-NaN row against the exact model in
+    every bit"""
+    run_workers(2, "device", ["accumulate_fp"], tmp_path, gpu=True, timeout=240)
+
+
+@pytest.mark.multipe
+@pytest.mark.parametrize("npes", [2, 4])
+def test_accumulate_arrival_orders(tmp_path, npes):
+    """worker test accumulate_orders on the device heap: full-mantissa arrays
+    from every PE at once; every element is the rounded sum in one of the
+    npes! arrival orders"""
+    run_workers(npes, "device", ["accumulate_orders"], tmp_path, gpu=True, timeout=240)
 
 
 def oshrun(exe, npes, *args):
@@ -188,7 +212,10 @@ def test_accumulate_kernel_alone(shm, arena, pass_elems, dtype):
     """n in {0, 1, 63, 64, 65, 255, 256, 257, pass - 1, pass + 1, 3 passes + 5}
     with target and source 1, 2 and 3 elements off a 16-byte boundary,
     independently (all nine pairs at the small sizes, three at the large
-    ones); sentinels around the target and the source stay as they were."""
+    ones); sentinels around the target and the source stay as they were.
+    Float and double operands are small integers, every sum exact: what the
+    add does when it rounds, underflows, overflows or meets a zero, an Inf or
+    a NaN is test_accumulate_kernel_float_semantics'."""
     dt = NP[dtype]
     es = np.dtype(dt).itemsize
     base, nbytes = arena
@@ -229,6 +256,43 @@ def test_accumulate_kernel_alone(shm, arena, pass_elems, dtype):
         assert bad.size == 0, (dtype, n, to, so, bad[:4] - GUARD - to, got[bad[:4]], want[bad[:4]])
         src_after = shm.get(base + half, sbuf.size, dt)
         assert (src_after.view(np.uint8) == sbuf.view(np.uint8)).all(), (dtype, n, to, so, "source changed")
+
+
+@pytest.mark.parametrize("dtype", ["float", "double"])
+def test_accumulate_kernel_float_semantics(shm, arena, dtype):
+    """the operand table of tests/_fp_add_cases.py through the kernel alone,
+    with target and source (0, 0), (1, 3) and (3, 1) elements off a 16-byte
+    boundary, and once more in reversed row order (every class in other lanes
+    and unroll slots): every non-NaN row equals one correctly rounded IEEE
+    add -- nearest-even, gradual underflow, overflow to Inf, zero signs -- in
+    every bit, every NaN row is a NaN; sentinels and source stay as they were.
+    The table's length is the size: many blocks, all four unroll slots."""
+    F = fp.FORMATS[dtype]
+    dt, es = F.np_float, np.dtype(F.np_float).itemsize
+    base, nbytes = arena
+    half = (nbytes // 2) & ~255
+    t, s = fp.cases(dtype)
+    n = t.size
+    assert n > 4 * 1024 and GUARD * es % 16 == 0 and base % 16 == 0 and half % 16 == 0
+    fwd = np.arange(n)
+    SENT = np.array([-12345.0], dt).view(F.np_uint)[0]
+    for to, so, order in ((0, 0, fwd), (1, 3, fwd), (3, 1, fwd), (1, 3, fwd[::-1])):
+        tbuf = np.full(GUARD + to + n + GUARD, SENT, F.np_uint)      # bit patterns: no NaN passes through a float move
+        sbuf = np.full(GUARD + so + n + GUARD, SENT, F.np_uint)
+        tbuf[GUARD + to: GUARD + to + n] = t.view(F.np_uint)[order]
+        sbuf[GUARD + so: GUARD + so + n] = s.view(F.np_uint)[order]
+        assert tbuf.nbytes <= half and sbuf.nbytes <= half
+        shm.put(base, tbuf)
+        shm.put(base + half, sbuf)
+        rc = shm.atomic_add_v_raw(dtype, base + (GUARD + to) * es, base + half + (GUARD + so) * es, n)
+        assert rc == 0, (dtype, to, so, rc)
+        shm.sync()
+        got = shm.get(base, tbuf.size, F.np_uint)
+        where = f"kernel alone, target +{to}, source +{so}, rows {'reversed' if order[0] else 'in order'}"
+        msg = fp.mismatches(dtype, got[GUARD + to: GUARD + to + n], order=order, where=where)
+        assert msg is None, msg
+        assert (got[:GUARD + to] == SENT).all() and (got[GUARD + to + n:] == SENT).all(), (where, "sentinels changed")
+        assert (shm.get(base + half, sbuf.size, F.np_uint) == sbuf).all(), (where, "source changed")
 
 
 # ---------------------------------------------------------------------------
