@@ -112,6 +112,37 @@ int mi355_combine_orders (int op, int dtype, void *const *dsts, const void *cons
 int mi355_combine_prefix (int op, int dtype, void *const *dsts, const void *const *srcs,
                           int nsrc, size_t n, void *stream);
 
+/* The value-and-location fold (loc.hip; shmemx_<T>_maxloc_to_all / _minloc_to_all).
+ * op: MI355_OP_MIN or MI355_OP_MAX. dtype: SHORT, INT, LONG, LONGLONG, FLOAT,
+ * DOUBLE, HALF, BFLOAT16. Source j contributes the pair (src_vals[j][i],
+ * src_locs[j][i]) for each i < n; src_locs, or any single entry of it, may be
+ * NULL: source j's location is then loc_base + j for every element. The result
+ * is the left fold over the sources in ascending order,
+ *   acc = beats (cand_j, acc) ? cand_j : acc,    starting from source 0's pair,
+ * where b beats a when (maxloc; minloc: < for >)
+ *   b.v is a NaN and (a.v is not a NaN, or b.l < a.l), or
+ *   neither is a NaN and (b.v > a.v, or (b.v == a.v and b.l < a.l)).
+ * A NaN beats every number in both operators; -0 == +0; half and bfloat16
+ * compare by their exact float values; integers have no NaN branch; a
+ * candidate equal in class and location does not beat (the earlier source
+ * stays). The winner's value bits go to dst_val[i] unchanged (NaN payload, zero
+ * sign, 16-bit pattern) and its location to dst_loc[i].
+ * 1 <= nsrc <= MI355_ORDERS_MAX_SOURCES; nsrc == 1 is a copy (or, with an
+ * implicit location, a fill of dst_loc). More sources run as several calls:
+ * entry 0 of the next call is the previous output with its explicit location
+ * array, the further entries stay implicit with loc_base advanced (loc_plan.h,
+ * mi355_loc_chunk_at). dst_val / dst_loc may alias src_vals[q] / src_locs[q]
+ * exactly, for one q; other overlaps are undefined. Sources may be peer (xGMI)
+ * pointers. Pointers element-aligned (locations: 8 bytes); when all of them are
+ * 16-byte aligned the kernel moves 16-byte vectors (loc_fold_vec), else one
+ * element per lane (loc_fold_elem); the same bits either way.
+ * MI355_E_UNSUP for any other op or dtype, MI355_E_INVAL for a bad count or
+ * pointer, both before anything is launched (and before any HIP call); n == 0
+ * launches nothing, fires an armed signal and returns 0. */
+int mi355_combine_loc (int op, int dtype, void *dst_val, long *dst_loc,
+                       const void *const *src_vals, const long *const *src_locs, long loc_base,
+                       int nsrc, size_t n, void *stream);
+
 /* nseg independent byte copies dsts[i] <- srcs[i] of nbytes[i] bytes in ONE
  * launch (the all-gather leg of the shard schedule). nseg <= 64. */
 int mi355_copy_segments (void *const *dsts, const void *const *srcs,

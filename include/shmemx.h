@@ -819,6 +819,73 @@ void shmemx_longlong_atomic_add_v (long long *target, const long long *source, s
 void shmemx_float_atomic_add_v (float *target, const float *source, size_t nelems, int pe);
 void shmemx_double_atomic_add_v (double *target, const double *source, size_t nelems, int pe);
 
+/* ---- value and location: maxloc / minloc reductions (MPI_MAXLOC / MPI_MINLOC) ----
+ * shmemx_<T>_maxloc_to_all / _minloc_to_all for T = short, int, long, longlong,
+ * float, double, half, bfloat16. Member j of the active set (its index in the
+ * set, 0 .. PE_size - 1) contributes, for each i < nreduce, the candidate pair
+ * (source[i], source_loc[i]); with source_loc == NULL the location is the
+ * member index j (not the PE number). b beats a for maxloc when
+ *   b.v is a NaN and (a.v is not a NaN, or b.l < a.l), or
+ *   neither is a NaN and (b.v > a.v, or (b.v == a.v and b.l < a.l));
+ * minloc has < for > on the values. A NaN beats every number in BOTH operators:
+ * it propagates and reports where it is, as torch.max / torch.min do. -0 and +0
+ * are equal (the smaller location decides); half and bfloat16 compare by their
+ * exact float values; integers have no NaN branch. The result is the left fold
+ * over members 0, 1, ... in ascending order from member 0's pair,
+ *   acc = beats (cand_j, acc) ? cand_j : acc,
+ * so two candidates that tie in class and in location keep the lower member.
+ * The winner's value bits arrive in target[i] unchanged (NaN payload, zero
+ * sign, 16-bit pattern), its location in target_loc[i]; every member receives
+ * the same pair, and nothing is rounded, so the bits do not depend on the
+ * schedule.
+ * Collective and blocking; nreduce == 0 still synchronizes ("barrier-only").
+ * All four arrays lie in the device symmetric heap (shmemx_malloc_device); any
+ * other memory aborts with a message naming the function and the argument --
+ * host arrays are not staged. target == source together with target_loc ==
+ * source_loc is allowed (in place); any other overlap between the arrays is
+ * undefined. There is no pWrk or pSync: nothing would use them.
+ * Schedule (shmemx_last_call_info: "loc-p2p"; "loc-local" for a one-member set,
+ * which is one local fold with no barrier): barrier, every member folds its
+ * shard (mi355_shard_bounds; the same element range of the 8-byte locations)
+ * of every member's arrays into its own target / target_loc, barrier, one copy
+ * launch pulls the other owners' value and location shards from their targets,
+ * barrier. Host barriers only. Sets above 32 members chain fold launches.
+ * Not built: long double and complex; a stream-ordered or graph-captured form;
+ * the fused one-launch kernel and the persistent server; RCCL; Fortran
+ * wrappers; a pshmem_ twin; the SHMEM_DEBUG argument exchange. */
+void shmemx_short_maxloc_to_all (short *target, long *target_loc, const short *source, const long *source_loc,
+        int nreduce, int PE_start, int logPE_stride, int PE_size);
+void shmemx_short_minloc_to_all (short *target, long *target_loc, const short *source, const long *source_loc,
+        int nreduce, int PE_start, int logPE_stride, int PE_size);
+void shmemx_int_maxloc_to_all (int *target, long *target_loc, const int *source, const long *source_loc,
+        int nreduce, int PE_start, int logPE_stride, int PE_size);
+void shmemx_int_minloc_to_all (int *target, long *target_loc, const int *source, const long *source_loc,
+        int nreduce, int PE_start, int logPE_stride, int PE_size);
+void shmemx_long_maxloc_to_all (long *target, long *target_loc, const long *source, const long *source_loc,
+        int nreduce, int PE_start, int logPE_stride, int PE_size);
+void shmemx_long_minloc_to_all (long *target, long *target_loc, const long *source, const long *source_loc,
+        int nreduce, int PE_start, int logPE_stride, int PE_size);
+void shmemx_longlong_maxloc_to_all (long long *target, long *target_loc, const long long *source, const long *source_loc,
+        int nreduce, int PE_start, int logPE_stride, int PE_size);
+void shmemx_longlong_minloc_to_all (long long *target, long *target_loc, const long long *source, const long *source_loc,
+        int nreduce, int PE_start, int logPE_stride, int PE_size);
+void shmemx_float_maxloc_to_all (float *target, long *target_loc, const float *source, const long *source_loc,
+        int nreduce, int PE_start, int logPE_stride, int PE_size);
+void shmemx_float_minloc_to_all (float *target, long *target_loc, const float *source, const long *source_loc,
+        int nreduce, int PE_start, int logPE_stride, int PE_size);
+void shmemx_double_maxloc_to_all (double *target, long *target_loc, const double *source, const long *source_loc,
+        int nreduce, int PE_start, int logPE_stride, int PE_size);
+void shmemx_double_minloc_to_all (double *target, long *target_loc, const double *source, const long *source_loc,
+        int nreduce, int PE_start, int logPE_stride, int PE_size);
+void shmemx_half_maxloc_to_all (shmemx_half_t *target, long *target_loc, const shmemx_half_t *source, const long *source_loc,
+        int nreduce, int PE_start, int logPE_stride, int PE_size);
+void shmemx_half_minloc_to_all (shmemx_half_t *target, long *target_loc, const shmemx_half_t *source, const long *source_loc,
+        int nreduce, int PE_start, int logPE_stride, int PE_size);
+void shmemx_bfloat16_maxloc_to_all (shmemx_bfloat16_t *target, long *target_loc, const shmemx_bfloat16_t *source, const long *source_loc,
+        int nreduce, int PE_start, int logPE_stride, int PE_size);
+void shmemx_bfloat16_minloc_to_all (shmemx_bfloat16_t *target, long *target_loc, const shmemx_bfloat16_t *source, const long *source_loc,
+        int nreduce, int PE_start, int logPE_stride, int PE_size);
+
 #ifdef __cplusplus
 }
 #endif

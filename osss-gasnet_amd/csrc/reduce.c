@@ -48,6 +48,7 @@
 #include "shmem.h"
 #include "shmemx.h"
 #include "shmemi.h"
+#include "loc_plan.h"
 #include "prefix_plan.h"
 #include "sched_plan.h"
 
@@ -1775,3 +1776,201 @@ SCAN_MINMAX (float, float, MI355_FLOAT)
 SCAN_MINMAX (longdouble, long double, MI355_LONGDOUBLE)
 SCAN_MINMAX (half, shmemx_half_t, MI355_HALF)
 SCAN_MINMAX (bfloat16, shmemx_bfloat16_t, MI355_BFLOAT16)
+
+/* ---------------------------------------------------------------------- */
+/* value and location: shmemx_<T>_maxloc_to_all / _minloc_to_all (shmemx.h) */
+/* ---------------------------------------------------------------------- */
+/* The host-synchronised row of the shard schedule with a pair of arrays on
+ * each side: barrier (every source is ready), the owner folds its shard of
+ * every member's values and locations into its own target and target_loc
+ * (mi355_combine_loc; the same element range of both), barrier, one copy
+ * launch pulls the other owners' two shards from their targets, barrier.
+ * Nothing is rounded and the owner presents the members in ascending order,
+ * so every member holds the same bits whatever the shard bounds are. In
+ * place (target == source and target_loc == source_loc) the owner's output
+ * aliases its own entry of the fold, which the kernel allows.
+ *
+ * Not built (shmemx.h says the same): long double and complex, a
+ * stream-ordered or graph-captured form, the fused one-launch kernel, the
+ * persistent server, RCCL, Fortran wrappers, the SHMEM_DEBUG argument
+ * exchange, staging of host arrays. */
+
+struct loc_call {
+    int op, dtype;
+    size_t es;
+    size_t t_off, tl_off, s_off, sl_off; /* heap offsets; sl_off is unused when implicit */
+    int implicit;                        /* source_loc == NULL: the location is the member index */
+};
+
+/* The owner's fold of elements [lo, hi) over every member, signalled and
+ * waited. Up to 32 members: one launch into the target. Above: chained
+ * launches (loc_plan.h), the running pair carried in scratch buffers A
+ * (values) and B (locations) so that an in-place target still holds this
+ * member's source when its turn comes; the range is walked in pieces whose
+ * locations fit buffer B. */
+static void loc_fold_range (const struct loc_call *c, const struct aset *s, size_t lo, size_t hi)
+{
+    const int chunks = mi355_loc_chunk_count (s->size);
+    const size_t piece = chunks == 1 ? hi - lo : shmemi.scratch_chunk / sizeof (long);
+    void *carry_val = shmemi.heap + shmemi.scratch_off;
+    long *carry_loc = (long *) (shmemi.heap + shmemi.scratch_off + shmemi.scratch_chunk);
+    if (piece == 0)
+        shmemi_fatal ("SHMEM_DEVICE_SCRATCH_SIZE is too small for a value-and-location fold over %d members", s->size);
+    for (size_t b = lo; b < hi; b += piece) {
+        const size_t e = hi - b < piece ? hi : b + piece, len = e - b;
+        for (int k = 0; k < chunks; ++k) {
+            const mi355_loc_chunk ck = mi355_loc_chunk_at (s->size, k);
+            const void *sv[MI355_LOC_MAX_SOURCES];
+            const long *sl[MI355_LOC_MAX_SOURCES];
+            if (ck.lead) {
+                sv[0] = carry_val;
+                sl[0] = carry_loc;
+            }
+            for (int i = 0; i < ck.take; ++i) {
+                const int pe = aset_pe (s, ck.first + i);
+                sv[ck.lead + i] = shmemi_peer_ptr (pe, c->s_off + b * c->es);
+                sl[ck.lead + i] = c->implicit ? NULL : (const long *) shmemi_peer_ptr (pe, c->sl_off + b * sizeof (long));
+            }
+            void *dv = ck.final ? shmemi_peer_ptr (shmemi.mype, c->t_off + b * c->es) : carry_val;
+            long *dl = ck.final ? (long *) shmemi_peer_ptr (shmemi.mype, c->tl_off + b * sizeof (long)) : carry_loc;
+            const int last = ck.final && e == hi;
+            if (last) {
+                shmemi_timed_begin ();
+                shmemi_arm_signal ();
+            }
+            const int rc = mi355_combine_loc (c->op, c->dtype, dv, dl, sv, sl, ck.loc_shift, ck.lead + ck.take, len,
+                                              shmemi.stream);
+            if (last)
+                shmemi_timed_end ();
+            if (rc != 0)
+                shmemi_fatal ("value-and-location kernel launch failed (op %d, dtype %d, %d members, %zu elements): %d",
+                              c->op, c->dtype, s->size, len, rc);
+        }
+    }
+    note_call (0, s->size, 1, s->size - 1, (unsigned long long) ((hi - lo) * (c->es + sizeof (long))), 0, 0,
+               mi355_last_kernel ());
+    shmemi_wait_signal ();
+}
+
+static void loc_p2p (const struct loc_call *c, const struct aset *s, size_t n)
+{
+    size_t lo, hi;
+    mi355_shard_bounds (n, c->es, s->size, s->me, &lo, &hi);
+    host_order ();
+    shmemi_barrier_set (s->start, s->stride, s->size); /* every source is ready */
+    if (hi > lo) {
+        shmemi_peer_acquire (shmemi.stream);
+        loc_fold_range (c, s, lo, hi);
+    }
+    shmemi_barrier_set (s->start, s->stride, s->size); /* every shard is folded */
+    shmemi_peer_acquire (shmemi.stream);
+
+    /* the other owners' shards, values and locations: 2 (N - 1) segments */
+    const size_t m = 2 * (size_t) s->size;
+    void **dsts = (void **) malloc (m * (2 * sizeof (void *) + sizeof (size_t)));
+    if (dsts == NULL)
+        shmemi_fatal ("out of host memory");
+    const void **sp = (const void **) (dsts + m);
+    size_t *nb = (size_t *) (sp + m);
+    int k = 0;
+    for (int i = 0; i < s->size; ++i) {
+        size_t l, h;
+        mi355_shard_bounds (n, c->es, s->size, i, &l, &h);
+        if (i == s->me || h <= l)
+            continue;
+        dsts[k] = shmemi_peer_ptr (shmemi.mype, c->t_off + l * c->es);
+        sp[k] = shmemi_peer_ptr (aset_pe (s, i), c->t_off + l * c->es);
+        nb[k++] = (h - l) * c->es;
+        dsts[k] = shmemi_peer_ptr (shmemi.mype, c->tl_off + l * sizeof (long));
+        sp[k] = shmemi_peer_ptr (aset_pe (s, i), c->tl_off + l * sizeof (long));
+        nb[k++] = (h - l) * sizeof (long);
+    }
+    copy_wait (dsts, sp, nb, k, 1);
+    free (dsts);
+    shmemi_barrier_set (s->start, s->stride, s->size); /* peers are done reading this target */
+}
+
+static void loc_impl (int op, int dtype, const char *fn, void *target, long *target_loc, const void *source,
+                      const long *source_loc, int nreduce, int PE_start, int logPE_stride, int PE_size)
+{
+    struct aset s;
+    shmemi_init_check (fn);
+    aset_init (fn, &s, PE_start, logPE_stride, PE_size);
+    if (nreduce < 0)
+        shmemi_fatal ("%s: nreduce %d < 0", fn, nreduce);
+    if (nreduce == 0) {
+        begin_call ("barrier-only");
+        shmemi_barrier_set (s.start, s.stride, s.size);
+        shmemi_barrier_set (s.start, s.stride, s.size);
+        return;
+    }
+    if (shmemi.heap == NULL)
+        shmemi_fatal ("%s: no GPU: this library reduces on the GPU only (SHMEM_BOOTSTRAP_ONLY set?)", fn);
+    const size_t n = (size_t) nreduce, es = mi355_dtype_size (dtype);
+    const struct {
+        const char *name;
+        const void *p;
+        size_t nbytes;
+        int optional;
+    } args[4] = {{"target", target, n * es, 0},
+                 {"target_loc", target_loc, n * sizeof (long), 0},
+                 {"source", source, n * es, 0},
+                 {"source_loc", source_loc, n * sizeof (long), 1}};
+    for (int i = 0; i < 4; ++i) {
+        if (args[i].p == NULL && args[i].optional)
+            continue;
+        if (args[i].p == NULL)
+            shmemi_fatal ("%s: NULL %s", fn, args[i].name);
+        if (ptr_kind (args[i].p, args[i].nbytes) != PK_DEV_SYM)
+            shmemi_fatal ("%s: %s (%p, %zu bytes) is not in the device symmetric heap; the value-and-location "
+                          "reductions take device-heap (shmemx_malloc_device) arrays only", fn, args[i].name,
+                          args[i].p, args[i].nbytes);
+    }
+    if (s.size > 1 && shmemi.p2p_broken)
+        shmemi_fatal ("%s: peer GPU memory reads failed the init self-test; the value-and-location reductions "
+                      "need them", fn);
+    shmemi_order_after_caller (0); /* SHMEM_ENTRY_SYNC */
+    caller_order_pending = s.size > 1;
+    const struct loc_call c = {op, dtype, es, shmemi_heap_offset (target), shmemi_heap_offset (target_loc),
+                               shmemi_heap_offset (source), source_loc != NULL ? shmemi_heap_offset (source_loc) : 0,
+                               source_loc == NULL};
+    SHMEMI_TRACE (SHMEMI_LOG_REDUCTION, "%s: nreduce %d, PE_start %d, logPE_stride %d, PE_size %d; %s locations%s",
+                  fn, nreduce, PE_start, logPE_stride, PE_size, c.implicit ? "member-index" : "explicit",
+                  target == source && (c.implicit || (const long *) target_loc == source_loc) ? ", in place" : "");
+    if (s.size == 1) {
+        SHMEMI_TRACE (SHMEMI_LOG_REDUCTION, "schedule: value and location, one member: one local fold, no barrier");
+        begin_call ("loc-local");
+        loc_fold_range (&c, &s, 0, n);
+        return;
+    }
+    SHMEMI_TRACE (SHMEMI_LOG_REDUCTION, "schedule: value and location, P2P shards, host barriers: fold of values "
+                                        "and locations, one gather of both (%zu elements, %d members%s)", n, s.size,
+                  mi355_loc_chunk_count (s.size) > 1 ? ", chained fold launches" : "");
+    begin_call ("loc-p2p");
+    loc_p2p (&c, &s, n);
+}
+
+#define SHMEMX_LOC(Name, Type, DT)                                                                              \
+    void shmemx_##Name##_maxloc_to_all (Type *target, long *target_loc, const Type *source,                     \
+                                        const long *source_loc, int nreduce, int PE_start, int logPE_stride,    \
+                                        int PE_size)                                                            \
+    {                                                                                                           \
+        loc_impl (MI355_OP_MAX, DT, "shmemx_" #Name "_maxloc_to_all", target, target_loc, source, source_loc,   \
+                  nreduce, PE_start, logPE_stride, PE_size);                                                    \
+    }                                                                                                           \
+    void shmemx_##Name##_minloc_to_all (Type *target, long *target_loc, const Type *source,                     \
+                                        const long *source_loc, int nreduce, int PE_start, int logPE_stride,    \
+                                        int PE_size)                                                            \
+    {                                                                                                           \
+        loc_impl (MI355_OP_MIN, DT, "shmemx_" #Name "_minloc_to_all", target, target_loc, source, source_loc,   \
+                  nreduce, PE_start, logPE_stride, PE_size);                                                    \
+    }
+
+SHMEMX_LOC (short, short, MI355_SHORT)
+SHMEMX_LOC (int, int, MI355_INT)
+SHMEMX_LOC (long, long, MI355_LONG)
+SHMEMX_LOC (longlong, long long, MI355_LONGLONG)
+SHMEMX_LOC (float, float, MI355_FLOAT)
+SHMEMX_LOC (double, double, MI355_DOUBLE)
+SHMEMX_LOC (half, shmemx_half_t, MI355_HALF)
+SHMEMX_LOC (bfloat16, shmemx_bfloat16_t, MI355_BFLOAT16)

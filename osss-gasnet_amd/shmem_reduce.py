@@ -306,6 +306,54 @@ class Shmem:
                 raise ValueError("scan_tensors takes tensors from heap_tensor (the device symmetric heap)")
         self.scan(op, dtype, out.data_ptr(), x.data_ptr(), x.numel(), PE_start, logPE_stride, PE_size, exclusive)
 
+    # ---- value and location: maxloc / minloc (include/shmemx.h)
+    LOC_OPS = ("max", "min")
+    LOC_DTYPES = ("short", "int", "long", "longlong", "float", "double", "half", "bfloat16")
+
+    def loc_to_all(self, op, dtype, target, target_loc, source, source_loc, nreduce, PE_start=0, logPE_stride=0,
+                   PE_size=None):
+        """shmemx_<dtype>_<op>loc_to_all (op "max" or "min"): every member
+        receives, per element, the winning value in `target` (its bits
+        unchanged) and its location in `target_loc` (int64). source_loc=None
+        passes NULL: the location is the member's index in the active set.
+        All arrays in the device symmetric heap. Blocking."""
+        if op not in self.LOC_OPS or dtype not in self.LOC_DTYPES:
+            raise ValueError(f"no {op}loc_to_all for {dtype}")
+        if PE_size is None:
+            PE_size = self.n_pes()
+        f = self._typed_fn(f"shmemx_{dtype}_{op}loc_to_all", None, [_vp, _vp, _vp, _vp, _i, _i, _i, _i])
+        f(target, target_loc, source, source_loc, nreduce, PE_start, logPE_stride, PE_size)
+
+    def loc_to_all_tensors(self, op, out, out_idx, x, idx=None, PE_start=0, logPE_stride=0, PE_size=None):
+        """loc_to_all() on contiguous tensors from heap_tensor: `out` and `x`
+        of one dtype (int16/32/64, float32/64, float16, bfloat16), `out_idx`
+        and `idx` int64, all of one size; idx=None: the member index.
+        out is x together with out_idx is idx: in place."""
+        import torch
+        dtype = TORCH_DTYPES.get(str(x.dtype).replace("torch.", ""))
+        if dtype not in self.LOC_DTYPES:
+            raise TypeError(f"no {op}loc_to_all for {x.dtype}")
+        tensors = [out, out_idx, x] + ([idx] if idx is not None else [])
+        if out.dtype != x.dtype or any(t.dtype != torch.int64 for t in tensors[1::2]):
+            raise TypeError("out and x must have one dtype, out_idx and idx must be int64")
+        if any(t.numel() != x.numel() or not t.is_contiguous() or t.device.type != "cuda" for t in tensors):
+            raise ValueError("the tensors must be contiguous GPU tensors of one size")
+        for t in tensors:
+            if t.numel() and not self.lib.shmemx_is_device_symmetric(t.data_ptr()):
+                raise ValueError("loc_to_all_tensors takes tensors from heap_tensor (the device symmetric heap)")
+        self.loc_to_all(op, dtype, out.data_ptr(), out_idx.data_ptr(), x.data_ptr(),
+                        idx.data_ptr() if idx is not None else None, x.numel(), PE_start, logPE_stride, PE_size)
+
+    def combine_loc(self, op, dtype, dst_val, dst_loc, src_vals, src_locs, loc_base, n, stream=None):
+        """mi355_combine_loc: the value-and-location fold of len(src_vals)
+        sources. src_locs: None (all implicit), or a list whose entries may be
+        None (source j's location is then loc_base + j). Returns its status."""
+        f = self._typed_fn("mi355_combine_loc", _i, [_i, _i, _vp, _vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp),
+                                                     ctypes.c_long, _i, _sz, _vp])
+        sv = (_vp * max(1, len(src_vals)))(*src_vals)
+        sl = None if src_locs is None else (_vp * max(1, len(src_locs)))(*[x if x else None for x in src_locs])
+        return f(OPS.index(op), DTYPES.index(dtype), dst_val, dst_loc, sv, sl, loc_base, len(src_vals), n, stream)
+
     # ---- all-to-all (include/shmem.h)
     def _alltoall_fn(self, bits, strided):
         if bits not in (32, 64):
