@@ -37,3 +37,14 @@ def finite_source(op, dtype, n, seed, pe):
 def by_kind(kind, op, dtype, n, seed, pe):
     """the "inputs" entries of a stream case (tests/pe_worker.py run_stream)"""
     return {"finite": finite_source, "nan": nan_source, "default": source}[kind](op, dtype, n, seed, pe)
+
+
+def paths_source(op, dtype, n, spacing, member):
+    """Member `member`'s source of a directed-table case ("inputs": "paths"):
+    the operand table of tests/_op_paths.py spread over n elements, one row
+    every `spacing` elements among plain finite ones and repeated to the end.
+    Member 0 holds the accumulators and member 1 the incoming operands, so the
+    two meet as (acc, src) in the order the table names; further members hold
+    plain elements (the special result is carried on)."""
+    import _op_paths
+    return _op_paths.spaced_layout(op, dtype, n, spacing, member)

@@ -11,7 +11,8 @@ A case: {"id", "op", "dtype", "n", "set": [PE_start, logPE_stride, PE_size],
 "algorithm": auto | p2p | exact | rccl}. Member i's source is
 _scan_ref.sources(op, dtype, PE_size, n, seed)[i] (with "inputs": exhaustive |
 product, two members of a 16-bit float type: the first n of a and b of that
-pair set of tests/_half_ref.py). overlap_up / overlap_down:
+pair set of tests/_half_ref.py; with "inputs": "paths" and "spacing": member
+i's array of tests/_inputs.py paths_source). overlap_up / overlap_down:
 the target starts 16 elements above / below the source in one buffer. A
 "torch" case {"id", "torch": float32 | bfloat16, "op", "n", "excl", "seed"}
 runs Shmem.scan_tensors on heap_tensors over all PEs.
@@ -83,7 +84,10 @@ def run_scan(shm, c, me, bufs, out):
     j = mem_pes.index(me)
     op, dtype, n, excl, mode = c["op"], c["dtype"], c["n"], bool(c.get("excl")), c["mode"]
     es = np.dtype(S.NP[dtype]).itemsize
-    if "inputs" in c:    # the 16-bit floats' pair sets: a is member 0's source, b member 1's
+    if c.get("inputs") == "paths":   # the directed operand table (tests/_op_paths.py), by member index
+        import _inputs
+        srcs = [_inputs.paths_source(op, dtype, n, c["spacing"], i) for i in range(len(mem_pes))]
+    elif "inputs" in c:  # the 16-bit floats' pair sets: a is member 0's source, b member 1's
         srcs = [s[:n] for s in _half_ref.pair_set(c["inputs"], dtype)]
     else:
         srcs = S.sources(op, dtype, len(mem_pes), n, c["seed"])

@@ -420,6 +420,9 @@ def main():
         es = np.dtype(shmem_reduce.NP[dtype]).itemsize
         if "golden" in c:  # the committed fixture's inputs (tests/golden/), member i's row
             x = golden_source(c, op, dtype, n, members(*mine).index(me))
+        elif c.get("inputs") == "paths":  # the directed operand table (tests/_op_paths.py), by member index
+            import _inputs
+            x = _inputs.paths_source(op, dtype, n, c["spacing"], members(*mine).index(me))
         else:
             x = source(op, dtype, n, c["seed"], me)
         mode = c["mode"]

@@ -74,12 +74,9 @@ SOME = [("sum", "double"), ("sum", "float"), ("xor", "int"), ("and", "longlong")
         ("min", "short"), ("prod", "complexd"), ("sum", "longdouble")]
 
 
-@pytest.mark.parametrize("fused_max,oneshot_max", [("1M", "64K"), ("2M", "0"), ("0", "0")],
-                         ids=["fused-oneshot", "fused-twoshot-2M", "multi-launch"])
-def test_four_pes_all_44_pairs_p2p_and_exact(tmp_path, fused_max, oneshot_max):
-    """Every pair on 4 PEs, through the one-launch fused kernel (messages up to
-    1 MiB; one-shot fold up to 64 KiB, reduce-scatter + all-gather above) and
-    through the multi-launch shard schedule (fused path disabled)."""
+def four_pes_cases():
+    """the cases of test_four_pes_all_44_pairs_p2p_and_exact (tests/test_op_paths.py counts the
+    operator branches their inputs reach)"""
     cases = []
     cases += make_cases(oracle.PAIRS, 1000, [[0, 0, 4]], "dev", "p2p", 0)
     cases += make_cases(oracle.PAIRS, 257, [[0, 0, 4]], "dev", "exact", 100)
@@ -88,6 +85,16 @@ def test_four_pes_all_44_pairs_p2p_and_exact(tmp_path, fused_max, oneshot_max):
     cases += make_cases(SOME, 4099, [[1, 0, 3]], "dev", "p2p", 400)  # several blocks and an element tail
     cases += make_cases(oracle.PAIRS, 1000, [[0, 0, 4]], "dev", "p2p", 500, order="pe_start")
     cases += make_cases(SOME, 4099, [[0, 0, 4]], "inplace", "p2p", 600, order="pe_start")
+    return cases
+
+
+@pytest.mark.parametrize("fused_max,oneshot_max", [("1M", "64K"), ("2M", "0"), ("0", "0")],
+                         ids=["fused-oneshot", "fused-twoshot-2M", "multi-launch"])
+def test_four_pes_all_44_pairs_p2p_and_exact(tmp_path, fused_max, oneshot_max):
+    """Every pair on 4 PEs, through the one-launch fused kernel (messages up to
+    1 MiB; one-shot fold up to 64 KiB, reduce-scatter + all-gather above) and
+    through the multi-launch shard schedule (fused path disabled)."""
+    cases = four_pes_cases()
     results = run_pes(4, cases, tmp_path, extra_env={"SHMEM_FUSED_MAX_BYTES": fused_max,
                                                      "SHMEM_ONESHOT_MAX_BYTES": oneshot_max})
     check(results, cases)
