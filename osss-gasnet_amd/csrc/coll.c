@@ -51,6 +51,11 @@
  * fcollect queue barrier, copies and barrier on the library stream (device
  * barriers, one host wait); collect exchanges its counts through the host
  * bootstrap segment and keeps host barriers.
+ *
+ * tests/test_datamove_cpu.py (host heap, no GPU) and tests/test_gpu_datamove.py
+ * hold put / get, broadcast, fcollect and collect to the byte-exact model of
+ * tests/_datamove_ref.py at every byte phase and size edge, and assert the
+ * route or schedule each call takes.
  */
 #define _GNU_SOURCE
 #include <complex.h>
@@ -560,7 +565,10 @@ static void collect_bytes (const char *fn, void *target, const void *source, siz
                            int logPE_stride, int PE_size)
 {
     struct cset s = make_set (fn, PE_start, logPE_stride, PE_size);
-    const int host = source_kind (fn, source, nbytes);
+    /* a member that contributes nothing still reads the others' sources: the
+     * heap they are in is the heap of its own source pointer, whatever its
+     * count (source_kind alone calls a source of 0 bytes device memory) */
+    const int host = nbytes != 0 ? source_kind (fn, source, nbytes) : shmemi_in_host_heap (source, 0);
     shmemi_publish_count (nbytes);
     (void) collective_entry (fn, source, nbytes, &s, 0);
     size_t *counts = (size_t *) malloc (sizeof (size_t) * (size_t) s.size);
@@ -568,6 +576,11 @@ static void collect_bytes (const char *fn, void *target, const void *source, siz
         shmemi_fatal ("out of host memory");
     for (int i = 0; i < s.size; ++i)
         counts[i] = shmemi_peer_count (s.start + i * s.stride);
+    if (nbytes == 0 && !host && !shmemi_in_device_heap (source, 0))
+        for (int i = 0; i < s.size; ++i)
+            if (counts[i] != 0)
+                shmemi_fatal ("%s: source %p is not symmetric (allocate it with shmem_malloc or "
+                              "shmemx_malloc_device)", fn, source);
     gather_bytes (fn, target, source, counts, &s, 1, host);
     free (counts);
     shmemi_barrier_set (s.start, s.stride, s.size);

@@ -60,8 +60,11 @@ struct SegParams {
 // Where a segment's vector part starts: `head` bytes peeled so the target
 // starts on a 128-byte line (whole-line stores: a target 16 bytes off its
 // line cost the copy 96 us against 77 per 256 MiB, profiles/r05/cold/
-// linepeel_*.jsonl), then the source's phase against it (0: 16-byte aligned
-// too; otherwise copy_segments_shift).
+// linepeel_*.jsonl), then the source's phase against the target's (0: 16-byte
+// aligned too; otherwise copy_segments_shift). The phase is that of the
+// pointers, not of the source behind the head: a head cut short by nb ends
+// off the line, and a segment at ONE phase would be taken for a shifted one
+// (tests/test_gpu_datamove.py, put and get below 128 bytes at equal phases).
 struct SegPlan {
     uint64_t head;
     unsigned delta;
@@ -69,7 +72,7 @@ struct SegPlan {
 __host__ __device__ inline SegPlan seg_plan(const void *dst, const void *src, uint64_t nb) {
     uint64_t head = (128u - (unsigned)((uintptr_t)dst & 127)) & 127u;
     if (head > nb) head = nb;
-    return {head, (unsigned)(((uintptr_t)src + head) & 15)};
+    return {head, (unsigned)(((uintptr_t)src - (uintptr_t)dst) & 15)};
 }
 
 template <int UNROLL, int NS>

@@ -45,6 +45,9 @@ def dm_source(c, pe):
 
 
 def run_datamove(shm, c, me, da, db, ha, hb, results):
+    """One "putget", "broadcast", "fcollect" or "collect" case, element-aligned
+    and from buffer bases; every byte phase, size edge and route of these
+    calls: tests/test_gpu_datamove.py (tests/_datamove_worker.py)."""
     import ctypes
     kind, bits = c["kind"], c["bits"]
     dt = np.int32 if bits == 32 else np.int64

@@ -1,6 +1,8 @@
 """GPU: put/get, broadcast, fcollect and collect across PE processes
 (SURVEY.md 8f rows 3-4), checked against the oracle's restatement of the
-reference semantics (oracle.broadcast / fcollect / collect)."""
+reference semantics (oracle.broadcast / fcollect / collect). The same calls
+at every byte phase, size edge and route, against whole guarded images:
+tests/test_gpu_datamove.py."""
 import numpy as np
 import pytest
 
