@@ -143,6 +143,34 @@ int mi355_combine_loc (int op, int dtype, void *dst_val, long *dst_loc,
                        const void *const *src_vals, const long *const *src_locs, long loc_base,
                        int nsrc, size_t n, void *stream);
 
+/* The widening fold (wide.hip; shmemx_<T>_wsum_to_all / _wsum_to_all_float):
+ * the sum of nsrc half or bfloat16 arrays accumulated in binary32.
+ * dtype: MI355_HALF or MI355_BFLOAT16, the sources' type. out_dtype: the same
+ * type (dst holds n 16-bit elements) or MI355_FLOAT (dst holds n floats).
+ *   acc = (float) srcs[0][i]                          exact
+ *   acc = acc + (float) srcs[j][i]   j = 1 .. nsrc-1  IEEE binary32 add, to
+ *                                                     nearest even, subnormals kept
+ *   dst[i] = acc rounded once to the type (nearest even, subnormals kept,
+ *            overflow to +-inf), or acc itself for the float output
+ * A NaN result is 0x7E00 (half), 0x7FC0 (bfloat16) or 0x7FC00000 (float), at
+ * nsrc == 1 too: one source is a conversion, not a copy.
+ * 1 <= nsrc <= MI355_ORDERS_MAX_SOURCES. dst may alias srcs[q] exactly, for
+ * one q, when out_dtype == dtype; every other overlap is undefined. Sources
+ * may be peer (xGMI) pointers. Pointers element-aligned (2 bytes; a float dst
+ * 4). A lane's unit is one 16-byte store: 8 elements from a 16-byte load, or
+ * for the float output 4 from an 8-byte load. A 16-byte aligned dst with every
+ * source aligned to its load runs wide_fold_vec, with a source off that
+ * wide_fold_unal (unaligned loads), a dst off the 16-byte phase or less than
+ * one unit wide_fold_elem (one element per lane); the same bits in each.
+ * MI355_E_UNSUP for any other dtype or out_dtype, MI355_E_INVAL for a bad
+ * count or pointer, both before anything is launched (and before any HIP
+ * call); n == 0 launches nothing, fires an armed signal and returns 0.
+ * mi355_combine_wide_plan: the 16-byte-aligned launch's shape for n elements
+ * on `cus` compute units -- the grid (at least 1) and the elements one pass
+ * of that grid covers (grid x 256 lanes x 8 elements; float output: x 4). */
+int mi355_combine_wide (int dtype, int out_dtype, void *dst, const void *const *srcs, int nsrc, size_t n, void *stream);
+void mi355_combine_wide_plan (size_t n, int out_dtype, int cus, unsigned *grid, unsigned long long *pass);
+
 /* nseg independent byte copies dsts[i] <- srcs[i] of nbytes[i] bytes in ONE
  * launch (the all-gather leg of the shard schedule). nseg <= 64. */
 int mi355_copy_segments (void *const *dsts, const void *const *srcs,

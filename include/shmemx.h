@@ -886,6 +886,48 @@ void shmemx_bfloat16_maxloc_to_all (shmemx_bfloat16_t *target, long *target_loc,
 void shmemx_bfloat16_minloc_to_all (shmemx_bfloat16_t *target, long *target_loc, const shmemx_bfloat16_t *source, const long *source_loc,
         int nreduce, int PE_start, int logPE_stride, int PE_size);
 
+/* ---- wide sum: half / bfloat16 sums accumulated in binary32 ----
+ * shmemx_<T>_wsum_to_all (a result of the type) and shmemx_<T>_wsum_to_all_float
+ * (a float result) for T = half, bfloat16. With the members j = 0 .. PE_size - 1
+ * of the active set in ascending order, for each i < nreduce
+ *   acc = (float) source_0[i]                      exact
+ *   acc = acc + (float) source_j[i]                IEEE binary32 add: to nearest
+ *                                                  even, subnormals kept
+ *   target[i] = acc rounded once to T (to nearest even, subnormals kept, overflow
+ *               to +-inf), or acc itself (_float)
+ * on EVERY member, whatever SHMEM_REDUCE_ORDER / shmemx_set_reduce_order says:
+ * all members receive the same bits, independent of shard bounds and schedule.
+ * Unlike shmemx_<T>_sum_to_all, whose every step is rounded to the 16-bit type
+ * and whose members fold in their own orders from three members on, an
+ * intermediate beyond the type's range does not become an infinity (half:
+ * 60000 + 60000 - 60000 is 60000) and the low bits survive to the one rounding.
+ * A NaN result is the canonical quiet NaN (0x7E00, 0x7FC0, float: 0x7FC00000),
+ * in a one-member set too: that call converts, it does not copy bytes.
+ * Collective and blocking; nreduce == 0 still synchronizes ("barrier-only").
+ * Both arrays lie in the device symmetric heap (shmemx_malloc_device). There
+ * is no pWrk or pSync: nothing would use them. target == source is allowed for
+ * the 16-bit result (in place). The library aborts with a message naming the
+ * function and the argument for: any other overlap; a float target that
+ * overlaps the source at all; an array outside the device symmetric heap (host
+ * arrays are not staged, other device memory is not mapped); a NULL pointer;
+ * nreduce < 0; an active set above 32 members; peer reads that failed the init
+ * self-test.
+ * Schedule (shmemx_last_call_info: "wide-p2p"; "wide-local" for a one-member
+ * set, which is one local fold with no barrier): barrier, every member folds
+ * its shard (mi355_shard_bounds of the 2-byte source elements, so a float
+ * shard starts on a 512-byte boundary) of every member's source into its own
+ * target with one mi355_combine_wide launch (kernel mi355k::wide_fold_*),
+ * barrier, one copy launch pulls the other owners' shards from their targets,
+ * barrier. Host barriers only.
+ * Deliberately not built: a stream-ordered or graph-captured form; the fused
+ * one-launch kernel, the persistent server and RCCL; Fortran wrappers; host-heap
+ * or external (non-heap) buffers; prod, min and max (min and max round nothing,
+ * a wide product is a different contract); sets above 32 members. */
+void shmemx_half_wsum_to_all (shmemx_half_t *target, const shmemx_half_t *source, int nreduce, int PE_start, int logPE_stride, int PE_size);
+void shmemx_half_wsum_to_all_float (float *target, const shmemx_half_t *source, int nreduce, int PE_start, int logPE_stride, int PE_size);
+void shmemx_bfloat16_wsum_to_all (shmemx_bfloat16_t *target, const shmemx_bfloat16_t *source, int nreduce, int PE_start, int logPE_stride, int PE_size);
+void shmemx_bfloat16_wsum_to_all_float (float *target, const shmemx_bfloat16_t *source, int nreduce, int PE_start, int logPE_stride, int PE_size);
+
 #ifdef __cplusplus
 }
 #endif

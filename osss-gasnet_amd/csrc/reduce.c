@@ -1974,3 +1974,155 @@ SHMEMX_LOC (float, float, MI355_FLOAT)
 SHMEMX_LOC (double, double, MI355_DOUBLE)
 SHMEMX_LOC (half, shmemx_half_t, MI355_HALF)
 SHMEMX_LOC (bfloat16, shmemx_bfloat16_t, MI355_BFLOAT16)
+
+/* ---------------------------------------------------------------------- */
+/* wide sum: shmemx_<T>_wsum_to_all / _wsum_to_all_float (shmemx.h)         */
+/* ---------------------------------------------------------------------- */
+/* Half and bfloat16 sums accumulated in binary32 and rounded once, or not at
+ * all (mi355_combine_wide). The host-synchronised row of the shard schedule,
+ * as loc_p2p: barrier (every source is ready), the owner folds its shard of
+ * every member's source into its own target, barrier, one copy launch pulls
+ * the other owners' shards from their targets, barrier. The owner presents
+ * the members in ascending order whatever SHMEM_REDUCE_ORDER says, so every
+ * member holds the same bits, independent of the shard bounds; this
+ * collective does not go through plan_schedule. The bounds are those of the
+ * 2-byte source elements for both outputs, so a float shard starts on a
+ * 512-byte boundary. In place (target == source, 16-bit result) the owner's
+ * output aliases its own entry of the fold, which the kernel allows.
+ *
+ * Not built (shmemx.h says the same): stream-ordered, fused, persistent and
+ * RCCL forms, Fortran wrappers, host-heap or external buffers, prod, min and
+ * max, sets above 32 members. */
+
+struct wide_call {
+    int dtype, out_dtype;
+    size_t oes;          /* bytes of one target element: 2 or 4 */
+    size_t t_off, s_off; /* heap offsets */
+};
+
+/* The owner's fold of elements [lo, hi) over every member, signalled and waited. */
+static void wide_fold_range (const struct wide_call *c, const struct aset *s, size_t lo, size_t hi)
+{
+    const void *sv[MI355_ORDERS_MAX_SOURCES];
+    for (int i = 0; i < s->size; ++i)
+        sv[i] = shmemi_peer_ptr (aset_pe (s, i), c->s_off + lo * 2);
+    shmemi_timed_begin ();
+    shmemi_arm_signal ();
+    const int rc = mi355_combine_wide (c->dtype, c->out_dtype, shmemi_peer_ptr (shmemi.mype, c->t_off + lo * c->oes), sv,
+                                       s->size, hi - lo, shmemi.stream);
+    shmemi_timed_end ();
+    if (rc != 0)
+        shmemi_fatal ("wide sum kernel launch failed (dtype %d, out %d, %d members, %zu elements): %d", c->dtype,
+                      c->out_dtype, s->size, hi - lo, rc);
+    /* the sources and the output as 2-byte buffers; a float output's other half beyond them */
+    note_call (0, s->size, 1, s->size - 1, (unsigned long long) ((hi - lo) * 2),
+               (unsigned long long) ((hi - lo) * (c->oes - 2)), 0, mi355_last_kernel ());
+    shmemi_wait_signal ();
+}
+
+static void wide_p2p (const struct wide_call *c, const struct aset *s, size_t n)
+{
+    size_t lo, hi;
+    mi355_shard_bounds (n, 2, s->size, s->me, &lo, &hi);
+    host_order ();
+    shmemi_barrier_set (s->start, s->stride, s->size); /* every source is ready */
+    if (hi > lo) {
+        shmemi_peer_acquire (shmemi.stream);
+        wide_fold_range (c, s, lo, hi);
+    }
+    shmemi_barrier_set (s->start, s->stride, s->size); /* every shard is folded */
+    shmemi_peer_acquire (shmemi.stream);
+
+    /* the other owners' shards of the target: at most N - 1 segments */
+    void *dsts[MI355_ORDERS_MAX_SOURCES];
+    const void *sp[MI355_ORDERS_MAX_SOURCES];
+    size_t nb[MI355_ORDERS_MAX_SOURCES];
+    int k = 0;
+    for (int i = 0; i < s->size; ++i) {
+        size_t l, h;
+        mi355_shard_bounds (n, 2, s->size, i, &l, &h);
+        if (i == s->me || h <= l)
+            continue;
+        dsts[k] = shmemi_peer_ptr (shmemi.mype, c->t_off + l * c->oes);
+        sp[k] = shmemi_peer_ptr (aset_pe (s, i), c->t_off + l * c->oes);
+        nb[k++] = (h - l) * c->oes;
+    }
+    copy_wait (dsts, sp, nb, k, 1);
+    shmemi_barrier_set (s->start, s->stride, s->size); /* peers are done reading this target */
+}
+
+static void wide_impl (int dtype, int float_out, const char *fn, void *target, const void *source, int nreduce,
+                       int PE_start, int logPE_stride, int PE_size)
+{
+    struct aset s;
+    shmemi_init_check (fn);
+    aset_init (fn, &s, PE_start, logPE_stride, PE_size);
+    if (PE_size > MI355_ORDERS_MAX_SOURCES)
+        shmemi_fatal ("%s: PE_size %d: the wide sums take active sets of at most %d members", fn, PE_size,
+                      MI355_ORDERS_MAX_SOURCES);
+    if (nreduce < 0)
+        shmemi_fatal ("%s: nreduce %d < 0", fn, nreduce);
+    if (nreduce == 0) {
+        begin_call ("barrier-only");
+        shmemi_barrier_set (s.start, s.stride, s.size);
+        shmemi_barrier_set (s.start, s.stride, s.size);
+        return;
+    }
+    if (shmemi.heap == NULL)
+        shmemi_fatal ("%s: no GPU: this library reduces on the GPU only (SHMEM_BOOTSTRAP_ONLY set?)", fn);
+    const size_t n = (size_t) nreduce, oes = float_out ? sizeof (float) : 2;
+    const struct {
+        const char *name;
+        const void *p;
+        size_t nbytes;
+    } args[2] = {{"target", target, n * oes}, {"source", source, n * 2}};
+    for (int i = 0; i < 2; ++i) {
+        if (args[i].p == NULL)
+            shmemi_fatal ("%s: NULL %s", fn, args[i].name);
+        if (ptr_kind (args[i].p, args[i].nbytes) != PK_DEV_SYM)
+            shmemi_fatal ("%s: %s (%p, %zu bytes) is not in the device symmetric heap; the wide sums take "
+                          "device-heap (shmemx_malloc_device) arrays only", fn, args[i].name, args[i].p,
+                          args[i].nbytes);
+    }
+    const size_t t = (size_t) target, sr = (size_t) source;
+    if (t < sr + n * 2 && sr < t + n * oes && (float_out || t != sr))
+        shmemi_fatal (float_out ? "%s: the float target (%p, %zu bytes) overlaps source (%p, %zu bytes)"
+                                : "%s: target (%p, %zu bytes) and source (%p, %zu bytes) overlap without being equal",
+                      fn, target, n * oes, source, n * 2);
+    if (s.size > 1 && shmemi.p2p_broken)
+        shmemi_fatal ("%s: peer GPU memory reads failed the init self-test; the wide sums need them", fn);
+    shmemi_order_after_caller (0); /* SHMEM_ENTRY_SYNC */
+    caller_order_pending = s.size > 1;
+    const struct wide_call c = {dtype, float_out ? MI355_FLOAT : dtype, oes, shmemi_heap_offset (target),
+                                shmemi_heap_offset (source)};
+    SHMEMI_TRACE (SHMEMI_LOG_REDUCTION, "%s: nreduce %d, PE_start %d, logPE_stride %d, PE_size %d; %s result%s", fn,
+                  nreduce, PE_start, logPE_stride, PE_size, float_out ? "float" : "16-bit",
+                  target == source ? ", in place" : "");
+    if (s.size == 1) {
+        SHMEMI_TRACE (SHMEMI_LOG_REDUCTION, "schedule: wide sum, one member: one local fold, no barrier");
+        begin_call ("wide-local");
+        wide_fold_range (&c, &s, 0, n);
+        return;
+    }
+    SHMEMI_TRACE (SHMEMI_LOG_REDUCTION, "schedule: wide sum, P2P shards, host barriers: binary32 fold in ascending "
+                                        "member order, one gather (%zu elements, %d members)", n, s.size);
+    begin_call ("wide-p2p");
+    wide_p2p (&c, &s, n);
+}
+
+#define SHMEMX_WSUM(Name, Type, DT)                                                                               \
+    void shmemx_##Name##_wsum_to_all (Type *target, const Type *source, int nreduce, int PE_start,                \
+                                      int logPE_stride, int PE_size)                                              \
+    {                                                                                                             \
+        wide_impl (DT, 0, "shmemx_" #Name "_wsum_to_all", target, source, nreduce, PE_start, logPE_stride,        \
+                   PE_size);                                                                                      \
+    }                                                                                                             \
+    void shmemx_##Name##_wsum_to_all_float (float *target, const Type *source, int nreduce, int PE_start,         \
+                                            int logPE_stride, int PE_size)                                        \
+    {                                                                                                             \
+        wide_impl (DT, 1, "shmemx_" #Name "_wsum_to_all_float", target, source, nreduce, PE_start, logPE_stride,  \
+                   PE_size);                                                                                      \
+    }
+
+SHMEMX_WSUM (half, shmemx_half_t, MI355_HALF)
+SHMEMX_WSUM (bfloat16, shmemx_bfloat16_t, MI355_BFLOAT16)

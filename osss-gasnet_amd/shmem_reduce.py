@@ -354,6 +354,57 @@ class Shmem:
         sl = None if src_locs is None else (_vp * max(1, len(src_locs)))(*[x if x else None for x in src_locs])
         return f(OPS.index(op), DTYPES.index(dtype), dst_val, dst_loc, sv, sl, loc_base, len(src_vals), n, stream)
 
+    # ---- wide sum: half / bfloat16 sums accumulated in binary32 (include/shmemx.h)
+    WSUM_DTYPES = ("half", "bfloat16")
+
+    def wsum(self, dtype, out_float, target_ptr, source_ptr, n, PE_start=0, logPE_stride=0, PE_size=None):
+        """shmemx_<dtype>_wsum_to_all (out_float: _wsum_to_all_float): the sum
+        of the members' 16-bit sources accumulated in binary32 in ascending
+        member order and rounded once (or kept as float32); the same bits on
+        every member. Both arrays in the device symmetric heap. Blocking."""
+        if dtype not in self.WSUM_DTYPES:
+            raise ValueError(f"no wsum_to_all for {dtype}")
+        if PE_size is None:
+            PE_size = self.n_pes()
+        f = self._typed_fn(f"shmemx_{dtype}_wsum_to_all{'_float' if out_float else ''}", None,
+                           [_vp, _vp, _i, _i, _i, _i])
+        f(target_ptr, source_ptr, n, PE_start, logPE_stride, PE_size)
+
+    def wsum_tensors(self, out, x, PE_start=0, logPE_stride=0, PE_size=None):
+        """wsum() on contiguous tensors from heap_tensor: `x` float16 or
+        bfloat16, `out` of the same dtype (out is x: in place) or float32."""
+        import torch
+        dtype = TORCH_DTYPES.get(str(x.dtype).replace("torch.", ""))
+        if dtype not in self.WSUM_DTYPES:
+            raise TypeError(f"no wsum_to_all for {x.dtype}")
+        if out.dtype != x.dtype and out.dtype != torch.float32:
+            raise TypeError(f"out must be {x.dtype} or torch.float32, not {out.dtype}")
+        if any(t.numel() != x.numel() or not t.is_contiguous() or t.device.type != "cuda" for t in (out, x)):
+            raise ValueError("out and x must be contiguous GPU tensors of one size")
+        for t in (out, x):
+            if t.numel() and not self.lib.shmemx_is_device_symmetric(t.data_ptr()):
+                raise ValueError("wsum_tensors takes tensors from heap_tensor (the device symmetric heap)")
+        o, s, nb = out.data_ptr(), x.data_ptr(), x.numel() * 2
+        if o < s + nb and s < o + out.numel() * out.element_size() and (out.dtype != x.dtype or o != s):
+            raise ValueError("out overlaps x (only a 16-bit out that is x itself may: in place)")
+        self.wsum(dtype, out.dtype != x.dtype, o, s, x.numel(), PE_start, logPE_stride, PE_size)
+
+    def combine_wide(self, dtype, out_dtype, dst, srcs, n, stream=None):
+        """mi355_combine_wide: the binary32-accumulated sum of len(srcs) half
+        or bfloat16 arrays into dst (out_dtype: the same type, or "float").
+        Returns its status."""
+        f = self._typed_fn("mi355_combine_wide", _i, [_i, _i, _vp, ctypes.POINTER(_vp), _i, _sz, _vp])
+        sv = (_vp * max(1, len(srcs)))(*srcs)
+        return f(DTYPES.index(dtype), DTYPES.index(out_dtype), dst, sv, len(srcs), n, stream)
+
+    def combine_wide_plan(self, n, out_dtype, cus):
+        """(grid, elements per grid pass) of mi355_combine_wide's 16-byte-aligned launch"""
+        f = self._typed_fn("mi355_combine_wide_plan", None,
+                           [_sz, _i, _i, ctypes.POINTER(ctypes.c_uint), ctypes.POINTER(ctypes.c_ulonglong)])
+        g, p = ctypes.c_uint(), ctypes.c_ulonglong()
+        f(n, DTYPES.index(out_dtype), cus, ctypes.byref(g), ctypes.byref(p))
+        return g.value, p.value
+
     # ---- all-to-all (include/shmem.h)
     def _alltoall_fn(self, bits, strided):
         if bits not in (32, 64):
